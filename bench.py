@@ -1,7 +1,13 @@
 #!/usr/bin/env python3
 """bench.py -- throughput of the NTSC-CRT field-pass hot path on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times exactly K steps once with BATCHES_IN_FLIGHT batches in flight (`--streams` pins
+another number), writes the outputs of its last step if asked (--dump-outputs DIR: dump_outputs) and prints the result line;
+`ms_per_step` = the K steps' wall time / K, `value` = frames / that time.  Everything else below -- tuning the batches in
+flight, the per-kernel durations and `roofline` figures that take a run of their own, the CPU baseline, the extra workloads,
+the one-shot CLI timing and the multi-GPU workloads of a --gpus N run -- runs with --full only.
 
 N = 1 runs in this process.  N > 1: if the process was not started by torch.distributed.run (no WORLD_SIZE in the
 environment) it re-executes itself as `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr
@@ -13,17 +19,18 @@ CRT_SYSTEM_NTSC, interlaced (field parity alternates per frame), full colour, no
 "frames/sec" = field-passes/sec (one field-pass per input frame, as extra/video_convert.c:259-260 does).
 
 Batches in flight: consecutive steps are independent batches.  With S of them in flight step k runs on context k % S (its own
-stream, state, signal and picture buffers) and the launch sequences overlap on the chip.  S is tuned: the K steps are timed
-for S = 1, 2 and 3 (each bracketed by the barrier + synchronize) and the best one is `value`; `config.batches_in_flight_tuning`
-holds all three, `one_batch_in_flight` the S = 1 figure, `roofline.kernel_ms` is measured with ONE batch in flight.
-`--streams 1` pins S.  (profiles/r03_streams_sweep.txt)
+stream, state, signal and picture buffers) and the launch sequences overlap on the chip.  With --full S is tuned: the K steps
+are timed for S = 1, 2 and 3 (each bracketed by the barrier + synchronize) and the best one is `value`;
+`config.batches_in_flight_tuning` holds all three, `one_batch_in_flight` the S = 1 figure, `roofline.kernel_ms` is measured
+with ONE batch in flight.  `--streams 1` pins S.  (profiles/r03_streams_sweep.txt)
 
 Multi-GPU: one process per GPU, frames sharded by rank; the only collective on the data path is the RCCL broadcast of
 the settings blob from rank 0.  Default: weak scaling (fixed batch per GPU).  `--strong F` splits F frames of
 BASELINE configs[2] (1920x1080, noise 0) over the ranks (F = 512 is the configuration BASELINE states).
 
 Prints ONE JSON line (rank 0), the LAST line of stdout, at most 4 KB (compact_record(); the round-3 line had grown to
-23 KB and the driver, which keeps 8 KB of output, could not parse it).  Objects of the line:
+23 KB and the driver, which keeps 8 KB of output, could not parse it).  Objects of the line (a plain run: `roofline` with the
+end-to-end figures of the timed steps only, `pipeline_*`):
   roofline         dominant kernel vs the HBM roofline (bytes per SURVEY.md 8(d) / DESIGN.md section 5)
   cpu_baseline     the reference (oracle/_ref, unmodified sources) or the oracle port on the host cores: 1 core, and
                    all cores (independent processes)
@@ -32,8 +39,8 @@ Prints ONE JSON line (rank 0), the LAST line of stdout, at most 4 KB (compact_re
                    (64), VHS 832x624 (configs[3]), NES pattern 0 (configs[4]), small batches, PV-1000, bloom
   strong_scaling   (N = 1) configs[2] on one GPU: T(512 frames), T(64 frames = the per-GPU share at 8 GPUs) and the
                    speed-up 8 GPUs can reach at best, T512 / T64
-The complete record (every workload with its own roofline / cpu_baseline / tuning objects) goes to
-gpurun_out/bench_full.json (and --full-json PATH).
+The complete record (every workload with its own roofline / cpu_baseline / tuning objects) goes to --full-json PATH, and
+with --full by default to bench_full.json in the repository root.
 """
 import argparse
 import ctypes as C
@@ -50,6 +57,10 @@ sys.path.insert(0, os.path.join(ROOT, "ntsc-crt_amd"))
 HBM_PEAK_GBS = 8000.0          # MI355X spec (MI355X_MICROARCH.md); measured copy peak 6290
 VALU_SIMDS = 1024             # 256 CUs x 4 SIMDs
 VALU_CLOCK_HZ = 2.4e9          # peak engine clock (MI355X_MICROARCH.md); the kernels run at 2.2-2.3 GHz (GRBM_GUI_ACTIVE / duration)
+# batches in flight of a plain run: the candidate --full's tuning chose in every recorded headline run since round 5
+# (profiles/r05_bench_default.json, profiles/r06_bench_default*.json)
+BATCHES_IN_FLIGHT = 2
+DUMP_BYTES = 48 << 20          # --dump-outputs: the picture sample as float32 (the state arrays add 24 bytes per field)
 
 
 def geometry(system, w, h, outw, outh, scanlines, bloom=False):
@@ -207,9 +218,11 @@ def compact_record(full):
     if cfg.get("batches_in_flight_tuning"):      # S -> frames/sec
         out["config"]["batches_in_flight_fps"] = {s_: _r(v["value"], 5) for s_, v in cfg["batches_in_flight_tuning"].items()}
     rf = full.get("roofline") or {}
-    out["roofline"] = {k: _r(rf.get(k)) for k in ("bound", "kernel", "achieved", "peak", "unit", "frac", "traffic", "traffic_ratio",
-                                                  "traffic_dominant_kernel", "algorithmic_bytes_per_field", "kernel_own_frac", "pipeline_frac")}
-    out["roofline"]["kernel_ms"] = {k: _r(v) for k, v in (rf.get("kernel_ms") or {}).items() if v}
+    out["roofline"] = {k: _r(rf[k]) for k in ("bound", "kernel", "achieved", "peak", "unit", "frac", "traffic", "traffic_ratio",
+                                              "traffic_dominant_kernel", "algorithmic_bytes_per_field", "kernel_own_frac", "pipeline_frac")
+                       if k in rf}
+    if "kernel_ms" in rf:
+        out["roofline"]["kernel_ms"] = {k: _r(v) for k, v in rf["kernel_ms"].items() if v}
     if rf.get("traffic_source"):
         out["roofline"]["traffic_source"] = rf["traffic_source"].split(" (")[0]
     if "traffic_stale" in rf:
@@ -423,8 +436,31 @@ class Batches:
         self.crts, self.images, self.base, self.s = [], None, None, None
 
 
-def run_workload(torch, crtlib, shard, dist, dev, rank, world, local, wl, steps, warmup, cpu_seconds, with_cpu, traffic_file=None):
-    """One workload on this rank's GPU; returns the result record (rank 0) or None."""
+def dump_outputs(torch, crt, outdir):
+    """--dump-outputs: what a caller of crthip_fieldpass receives from the context that ran the last timed step, as .npy files --
+    picture.npy (float32 BGRA bytes; a fixed, seeded sample of DUMP_BYTES: whole fields, or rows of one field where a field alone
+    is larger, with their indices in picture_fields.npy / picture_rows.npy) and every field's hsync.npy / vsync.npy / rn.npy
+    (float64).  The caller has synchronised the device."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    rng = np.random.default_rng(2024)
+    n, h = crt.out.shape[0], crt.out.shape[1]
+    row_bytes = crt.out[0, 0].numel() * 4
+    fields = np.sort(rng.choice(n, min(n, max(1, DUMP_BYTES // (row_bytes * h))), replace=False))
+    rows = np.arange(h) if row_bytes * h <= DUMP_BYTES else np.sort(rng.choice(h, DUMP_BYTES // row_bytes, replace=False))
+    pic = crt.out[torch.from_numpy(fields).to(crt.out.device)][:, torch.from_numpy(rows).to(crt.out.device)]
+    arrays = {"picture": pic.cpu().numpy().astype(np.float32), "picture_fields": fields.astype(np.float64),
+              "picture_rows": rows.astype(np.float64)}
+    for name in ("hsync", "vsync", "rn"):
+        arrays[name] = np.asarray(crt.get(name), dtype=np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, name + ".npy"), a)
+
+
+def run_workload(torch, crtlib, shard, dist, dev, rank, world, local, wl, steps, warmup, cpu_seconds, with_cpu, traffic_file=None,
+                 full=True, dump_dir=None):
+    """One workload on this rank's GPU; returns the result record (rank 0) or None.  full=False: the plain run -- the K steps
+    timed once with a fixed number of batches in flight, no per-kernel run; dump_dir: dump_outputs() of the last timed step."""
     system, w, h, outw, outh = wl["system"], wl["w"], wl["h"], wl["outw"], wl["outh"]
     n, noise, scanlines, fir = wl["batch"], wl["noise"], wl["scanlines"], wl.get("fir", 0)
     nes = system in ("nes", "nesp0")
@@ -432,10 +468,10 @@ def run_workload(torch, crtlib, shard, dist, dev, rank, world, local, wl, steps,
     # and picture buffers), so with S of them step k runs on context k % S with its own stream and the launch sequences of S
     # batches overlap -- the latency-bound sync chain and the launch gaps of one under the vector- / store-bound kernels of
     # the others.  How much that gives depends on how the hardware queues happen to interleave (0 .. 25 % at 1080p from box
-    # to box and run to run, profiles/r03_streams_sweep.txt), so S is TUNED here: the same K steps are timed for every
+    # to box and run to run, profiles/r03_streams_sweep.txt), so with --full S is TUNED here: the same K steps are timed for every
     # candidate S and the best one is the result; all of them are reported (`batches_in_flight_tuning`).  --streams N pins it.
     want = wl.get("streams", 0)
-    cands = [1, 2, 3] if want <= 0 else [want]
+    cands = [want] if want > 0 else ([1, 2, 3] if full else [BATCHES_IN_FLIGHT])
     if wl.get("sequence") or wl.get("graph"):
         cands = [1]
     S = max(cands)
@@ -489,34 +525,41 @@ def run_workload(torch, crtlib, shard, dist, dev, rank, world, local, wl, steps,
     # chosen S is timed R more times and `value` is the median of THOSE (the selection samples are not reused: no winner's curse);
     # min / median / max of the final samples go out as `value_spread`.
     frames = wl.get("total_frames") or world * n             # frames of the whole job per step
-    R = max(1, int(wl.get("reps", 5)))
-    samples = {cand: [] for cand in cands}
-    for _ in range(R):
-        for cand in cands:
-            samples[cand].append(timed(cand))
-    med = lambda v: sorted(v)[len(v) // 2]
-    tuning = {cand: med(v) for cand, v in samples.items()}
-    S = min(tuning, key=lambda c_: tuning[c_])
-    final = sorted(timed(S) for _ in range(R)) if len(cands) > 1 else sorted(samples[S])
-    elapsed = med(final)
-    spread = {"reps": len(final), "min": frames * steps / final[-1], "median": frames * steps / elapsed, "max": frames * steps / final[0],
-              "unit": "frames/sec", "note": "the chosen S re-timed %d x %d steps after the selection; value = the median" % (len(final), steps)}
-    single = {"value": frames * steps / tuning[1], "unit": "frames/sec", "ms_per_step": 1e3 * tuning[1] / steps,
-              "spread": [frames * steps / max(samples[1]), frames * steps / min(samples[1])]} if 1 in tuning and len(tuning) > 1 else None
+    if full:
+        R = max(1, int(wl.get("reps", 5)))
+        samples = {cand: [] for cand in cands}
+        for _ in range(R):
+            for cand in cands:
+                samples[cand].append(timed(cand))
+        med = lambda v: sorted(v)[len(v) // 2]
+        tuning = {cand: med(v) for cand, v in samples.items()}
+        S = min(tuning, key=lambda c_: tuning[c_])
+        final = sorted(timed(S) for _ in range(R)) if len(cands) > 1 else sorted(samples[S])
+        elapsed = med(final)
+        spread = {"reps": len(final), "min": frames * steps / final[-1], "median": frames * steps / elapsed, "max": frames * steps / final[0],
+                  "unit": "frames/sec", "note": "the chosen S re-timed %d x %d steps after the selection; value = the median" % (len(final), steps)}
+        single = {"value": frames * steps / tuning[1], "unit": "frames/sec", "ms_per_step": 1e3 * tuning[1] / steps,
+                  "spread": [frames * steps / max(samples[1]), frames * steps / min(samples[1])]} if 1 in tuning and len(tuning) > 1 else None
+    else:
+        elapsed = timed(S)
+    # the last timed repetition ran S batches in flight (the chosen one), so its last step ran on context (steps - 1) % S
+    if dump_dir and rank == 0:
+        dump_outputs(torch, crts[(steps - 1) % S], dump_dir)
     launch_mode = "HIP graph of 2 steps, replayed" if graph is not None else "eager"
     if graph is not None:
         crt.use_stream(None)
         del graph
 
-    # per-kernel durations with HIP events on the launch stream (separate short run, same workload, ONE batch in flight:
-    # a kernel's duration next to another batch's kernels says nothing about the kernel)
-    crt.profile(True)
-    for k in range(min(steps, 5)):
-        step(k, 1)
-    prof = crt.profile_read()
-    crt.profile(False)
-    kern_ms = {k: (v[0] / max(min(steps, 5), 1)) for k, v in prof.items()}     # ms per step (a step may launch a kernel twice)
-    dom = max(kern_ms, key=lambda k: kern_ms[k])
+    if full:
+        # per-kernel durations with HIP events on the launch stream (separate short run, same workload, ONE batch in flight:
+        # a kernel's duration next to another batch's kernels says nothing about the kernel)
+        crt.profile(True)
+        for k in range(min(steps, 5)):
+            step(k, 1)
+        prof = crt.profile_read()
+        crt.profile(False)
+        kern_ms = {k: (v[0] / max(min(steps, 5), 1)) for k, v in prof.items()}     # ms per step (a step may launch a kernel twice)
+        dom = max(kern_ms, key=lambda k: kern_ms[k])
     B.close()
     del crt, crts, s, B
     torch.cuda.empty_cache()
@@ -526,6 +569,26 @@ def run_workload(torch, crtlib, shard, dist, dev, rank, world, local, wl, steps,
     total_frames = frames * steps
     fps = total_frames / elapsed
     abytes, own = algorithmic_bytes(system, w, h, 2 if nes else 4, outw, outh, 4, scanlines, 0)
+    rec = {
+        "name": wl["name"],
+        "value": fps, "unit": "frames/sec", "ms_per_step": 1e3 * elapsed / steps, "steps": steps,
+        "config": {"workload": wl["desc"], "fields_per_gpu_per_step": n, "frames_per_step": frames,
+                   "sharding": "frames by rank, RCCL broadcast of settings only",
+                   "mode": ("one video cut over the ranks (shard.sequence_sharded), %s exchange round(s) per step" % sorted(set(seq_rounds))
+                            if seq_rounds else "one video per GPU (crthip_sequence)") if wl.get("sequence")
+                           else "independent frames (crthip_fieldpass)",
+                   "launch": launch_mode,
+                   "batches_in_flight": S},
+        "roofline": {"bound": "hbm", "peak": HBM_PEAK_GBS, "unit": "GB/s", "algorithmic_bytes_per_field": abytes,
+                     # the whole launch sequence, end to end (wall clock of the timed region)
+                     "pipeline_achieved": abytes * n * steps / elapsed / 1e9,
+                     "pipeline_frac": abytes * n * steps / elapsed / 1e9 / HBM_PEAK_GBS},
+    }
+    if blob_crcs is not None:
+        rec["settings_blob_crc32_per_rank"] = blob_crcs
+        rec["settings_blob_crc32_rank0_before_broadcast"] = crc_root
+    if not full:
+        return rec
     achieved = abytes * n / (kern_ms[dom] * 1e-3) / 1e9 if kern_ms[dom] > 0 else 0.0
     own_gbs = own[dom] * n / (kern_ms[dom] * 1e-3) / 1e9 if kern_ms[dom] > 0 else 0.0
     traffic = None
@@ -566,52 +629,37 @@ def run_workload(torch, crtlib, shard, dist, dev, rank, world, local, wl, steps,
                                                   "kernel times measured in this run" % os.path.relpath(traffic_file, ROOT)}
         except Exception:
             traffic = None
-    rec = {
-        "name": wl["name"],
-        "value": fps, "unit": "frames/sec", "ms_per_step": 1e3 * elapsed / steps, "steps": steps, "value_spread": spread,
-        "config": {"workload": wl["desc"], "fields_per_gpu_per_step": n, "frames_per_step": frames,
-                   "sharding": "frames by rank, RCCL broadcast of settings only",
-                   "mode": ("one video cut over the ranks (shard.sequence_sharded), %s exchange round(s) per step" % sorted(set(seq_rounds))
-                            if seq_rounds else "one video per GPU (crthip_sequence)") if wl.get("sequence")
-                           else "independent frames (crthip_fieldpass)",
-                   "launch": launch_mode,
-                   "batches_in_flight": S,
-                   "batches_in_flight_tuning": {str(c_): {"value": frames * steps / e_, "ms_per_step": 1e3 * e_ / steps,
-                                                           "samples_ms_per_step": [round(1e3 * x / steps, 5) for x in samples[c_]]}
-                                                for c_, e_ in sorted(tuning.items())},
-                   "batches_in_flight_note": "step k runs on context / stream k %% S; every context is an independent batch of "
-                                             "fields_per_gpu_per_step television sets with its own state, signal and picture buffers; "
-                                             "S tuned: every candidate timed %d times (round robin), chosen on the medians, then re-timed for the result" % R},
-        "roofline": {"bound": "hbm", "kernel": "k_" + dom,
-                     # as specified: the field-pass's algorithmic bytes per launch / the dominant kernel's duration
-                     "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
-                     "traffic": traffic,
-                     "traffic_what": "HBM bytes of ALL kernels of one field-pass launch sequence (counters), to be read against algorithmic_bytes_per_field x fields",
-                     "traffic_ratio": (traffic / (abytes * n)) if traffic else None,
-                     "traffic_dominant_kernel": traffic_kernel,
-                     # the kernels changed since the PMC passes that produced `traffic` (hash of csrc/ differs)
-                     "traffic_stale": traffic_stale,
-                     # NOT measured in this run: PMC passes need rocprofv3 around the process (tools/prof_bench.sh)
-                     "traffic_source": ("static: %s (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE of the same workload, "
-                                        "calibrated per access pattern: profiles/r03_pmc_calibration.json)"
-                                        % os.path.relpath(traffic_file, ROOT)) if traffic is not None else None,
-                     "valu": valu,
-                     "algorithmic_bytes_per_field": abytes,
-                     "kernel_ms": kern_ms,
-                     # the dominant kernel on the bytes it moves itself
-                     "kernel_own_bytes_per_field": own[dom], "kernel_own_achieved": own_gbs,
-                     "kernel_own_frac": own_gbs / HBM_PEAK_GBS,
-                     # the whole launch sequence, end to end (wall clock of the timed region)
-                     "pipeline_achieved": abytes * n * steps / elapsed / 1e9,
-                     "pipeline_frac": abytes * n * steps / elapsed / 1e9 / HBM_PEAK_GBS,
-                     "note": "640x480-class workloads are integer-VALU bound (~37 ops/B, SURVEY.md 8(d)); 1080p leans on HBM writes"},
-    }
+    rec["value_spread"] = spread
+    rec["config"].update({
+        "batches_in_flight_tuning": {str(c_): {"value": frames * steps / e_, "ms_per_step": 1e3 * e_ / steps,
+                                               "samples_ms_per_step": [round(1e3 * x / steps, 5) for x in samples[c_]]}
+                                     for c_, e_ in sorted(tuning.items())},
+        "batches_in_flight_note": "step k runs on context / stream k %% S; every context is an independent batch of "
+                                  "fields_per_gpu_per_step television sets with its own state, signal and picture buffers; "
+                                  "S tuned: every candidate timed %d times (round robin), chosen on the medians, then re-timed for the result" % R})
+    rec["roofline"].update({
+        "kernel": "k_" + dom,
+        # as specified: the field-pass's algorithmic bytes per launch / the dominant kernel's duration
+        "achieved": achieved, "frac": achieved / HBM_PEAK_GBS,
+        "traffic": traffic,
+        "traffic_what": "HBM bytes of ALL kernels of one field-pass launch sequence (counters), to be read against algorithmic_bytes_per_field x fields",
+        "traffic_ratio": (traffic / (abytes * n)) if traffic else None,
+        "traffic_dominant_kernel": traffic_kernel,
+        # the kernels changed since the PMC passes that produced `traffic` (hash of csrc/ differs)
+        "traffic_stale": traffic_stale,
+        # NOT measured in this run: PMC passes need rocprofv3 around the process (tools/prof_bench.sh)
+        "traffic_source": ("static: %s (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE of the same workload, "
+                           "calibrated per access pattern: profiles/r03_pmc_calibration.json)"
+                           % os.path.relpath(traffic_file, ROOT)) if traffic is not None else None,
+        "valu": valu,
+        "kernel_ms": kern_ms,
+        # the dominant kernel on the bytes it moves itself
+        "kernel_own_bytes_per_field": own[dom], "kernel_own_achieved": own_gbs,
+        "kernel_own_frac": own_gbs / HBM_PEAK_GBS,
+        "note": "640x480-class workloads are integer-VALU bound (~37 ops/B, SURVEY.md 8(d)); 1080p leans on HBM writes"})
     if single is not None:
         single["pipeline_frac"] = abytes * n * steps / tuning[1] / 1e9 / HBM_PEAK_GBS
         rec["one_batch_in_flight"] = single
-    if blob_crcs is not None:
-        rec["settings_blob_crc32_per_rank"] = blob_crcs
-        rec["settings_blob_crc32_rank0_before_broadcast"] = crc_root
     if with_cpu:
         rec["cpu_baseline"] = cpu_baseline(system + ("fir%d" % fir if fir else ""), w, h, outw, outh, noise, scanlines, cpu_seconds,
                                            all_cores=wl.get("cpu_all_cores", False))
@@ -654,9 +702,15 @@ def main():
     ap.add_argument("--overlap", type=int, default=0, help="chunks alternating between two streams (0 = library default)")
     ap.add_argument("--shape", type=int, default=0, help="kernel shape: 0 auto, 1 lane-per-scanline, 2 scanline-parallel")
     ap.add_argument("--streams", type=int, default=0,
-                    help="independent batches in flight, each on its own stream and context (0 = tuned: 1, 2 and 3 are timed, the best is the result; 1 = off)")
+                    help="independent batches in flight, each on its own stream and context (0 = BATCHES_IN_FLIGHT, with --full tuned: "
+                         "1, 2 and 3 are timed, the best is the result; 1 = off)")
     ap.add_argument("--graph", action="store_true", help="time a replayed HIP graph of two steps instead of eager launches (measured: no difference)")
     ap.add_argument("--full-json", default="", help="also write the complete record (every workload's own objects) to this file")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beside the headline too: tuning of the batches in flight, per-kernel durations and "
+                         "roofline, CPU baseline, extra workloads, the one-shot CLI timing, a --gpus N run's multi-GPU workloads")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy (dump_outputs)")
     ap.add_argument("--dry-run", action="store_true", help="(tests) exercise launch / collectives / JSON without a GPU")
     ap.add_argument("--multi-gpu-workloads", action="store_true",
                     help="(tests) run what a --gpus N run adds to the headline -- 1080p weak, BASELINE configs[2] sharded over the ranks -- "
@@ -715,12 +769,12 @@ def main():
               shape=args.shape, sequence=args.sequence, desc=desc, cpu_all_cores=True, graph=args.graph, streams=args.streams)
     if args.strong:
         wl["first_frame"] = shard.shard_range(args.strong, rank, world)[0]
-    with_cpu = world == 1 and not args.no_cpu
+    with_cpu = world == 1 and args.full and not args.no_cpu
     rec = run_workload(torch, crtlib, shard, dist, dev, rank, world, local, wl, args.steps, args.warmup, args.cpu_seconds, with_cpu,
-                       traffic_file=os.path.join(ROOT, "profiles", "traffic.json"))
+                       traffic_file=os.path.join(ROOT, "profiles", "traffic.json"), full=args.full, dump_dir=args.dump_outputs)
 
     extras = []
-    if world == 1 and headline and not args.no_extra:
+    if world == 1 and headline and args.full and not args.no_extra:
         EX = [
             dict(name="1080p_batch2048", system="ntsc", w=1920, h=1080, outw=1920, outh=1080, batch=2048, noise=0, scanlines=1,
                  desc="NTSC 1920x1080 -> 1920x1080 BGRA, interlaced, noise 0, scanlines 1 (BASELINE configs[2] geometry, one GPU full)"),
@@ -751,15 +805,15 @@ def main():
             extras.append(r)
 
     mg = {}
-    if headline and ((world > 1 and not args.no_extra) or args.multi_gpu_workloads):
+    if headline and ((world > 1 and args.full and not args.no_extra) or args.multi_gpu_workloads):
         # `bench.py --gpus N` is the command the driver's scaling run issues -- it must report the 1080p
         # numbers of the north star too, not only the weak 640x480 headline
         for e in multi_gpu_workloads(world, rank, shard):
             mg[e["name"]] = run_workload(torch, crtlib, shard, dist, dev, rank, world, local, e, 20 if e["batch"] <= 512 else max(5, args.steps // 2), 3,
-                                         0.0, False, traffic_file=None)
+                                         0.0, False, traffic_file=None, full=args.full)
 
     cli = None
-    if world == 1 and headline and not args.no_extra and not args.no_cpu:
+    if world == 1 and headline and args.full and not args.no_extra and not args.no_cpu:
         # BASELINE configs[0] as stated: whole-process wall time of `ntsc -op 640 480 0 0 in.ppm out.ppm`, the reference binary
         # beside the same crt_main.c linked against the HIP drop-in library (tools/time_cli.py); None where the driver binaries
         # are not prebuilt
@@ -817,8 +871,8 @@ def main():
         # RCCL printf()s its library path into C stdio's buffer, which would be flushed at exit AFTER this line
         sys.stdout.flush()
         C.CDLL(None).fflush(None)
-        # the complete record goes to a file (gpurun_out/ comes back from the GPU box), the LAST stdout line is the compact one
-        full_paths = [os.path.join(ROOT, "gpurun_out", "bench_full.json")] + ([args.full_json] if args.full_json else [])
+        # the complete record goes to a file, the LAST stdout line is the compact one
+        full_paths = ([os.path.join(ROOT, "bench_full.json")] if args.full else []) + ([args.full_json] if args.full_json else [])
         for fp in full_paths:
             try:
                 os.makedirs(os.path.dirname(os.path.abspath(fp)), exist_ok=True)

@@ -62,9 +62,9 @@ def test_c_programs_over_the_node_library_are_built(lib):
         assert not any(n.startswith(("hip", "nccl", "orc_")) for n in wanted), "the C programs go through the C ABI only"
 
 
-def test_struct_sizes_match_header(lib):
+def test_struct_sizes_match_header(lib, tmp_path):
     hdr = '#include "crt_hip.h"\n#include <stdio.h>\nint main(void){printf("%zu %zu %zu\\n", sizeof(crthip_params), sizeof(crthip_state), sizeof(crthip_line));return 0;}\n'
-    exe = "/tmp/crthip_sizes"
+    exe = str(tmp_path / "crthip_sizes")
     subprocess.run(["gcc", "-std=c99", "-I" + os.path.join(ROOT, "include"), "-x", "c", "-", "-o", exe],
                    input=hdr.encode(), check=True)
     a, b, c = map(int, subprocess.run([exe], capture_output=True, check=True).stdout.split())

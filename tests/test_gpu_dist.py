@@ -44,7 +44,7 @@ def test_bench_multi_gpu_workloads_over_rccl():
     """what `bench.py --gpus N` adds to the headline on every rank -- 1080p weak and BASELINE configs[2] sharded over the ranks -- run
     here with the one rank there is, every collective through RCCL: the final line carries the north star's row"""
     j = _bench([sys.executable, "bench.py", "--gpus", "1", "--force-dist", "--multi-gpu-workloads", "--no-cpu", "--no-extra", "--steps", "4",
-                "--warmup", "1"])
+                "--warmup", "1", "--full"])
     ns = j["north_star"]
     assert ns["n_gpus"] == 1 and j["world_size_seen_by_rccl"] == 1
     assert ns["fps_640"] > 1e5 and ns["fps_1080p_weak"] > 1e5 and 0.3 < ns["frac_1080p_weak"] < 1.0
@@ -209,7 +209,7 @@ def test_bench_tunes_the_batches_in_flight_and_reports_every_candidate():
     import tempfile
     full = os.path.join(tempfile.mkdtemp(prefix="benchfull_"), "full.json")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--batch", "96", "--steps", "6", "--warmup", "1", "--no-cpu", "--no-extra",
-                        "--full-json", full], capture_output=True, text=True, timeout=600, cwd=ROOT)
+                        "--full", "--full-json", full], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     line = r.stdout.strip().splitlines()[-1]
     assert len(line) < 4096                                   # the driver keeps 8 KB of output
@@ -232,6 +232,6 @@ def test_bench_tunes_the_batches_in_flight_and_reports_every_candidate():
     assert c["roofline"]["kernel_ms"]["decode"] > 0 and c["roofline"]["frac"] > 0
     # pinned
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--batch", "96", "--steps", "4", "--warmup", "1", "--no-cpu", "--no-extra", "--streams", "1",
-                        "--full-json", full], capture_output=True, text=True, timeout=600, cwd=ROOT)
+                        "--full", "--full-json", full], capture_output=True, text=True, timeout=600, cwd=ROOT)
     j = json.load(open(full))
     assert j["config"]["batches_in_flight"] == 1 and sorted(j["config"]["batches_in_flight_tuning"]) == ["1"] and "one_batch_in_flight" not in j

@@ -17,7 +17,7 @@ res = {}
 for r in range(procs):
     for name, args in WL:
         for pad in ("1", "0"):
-            out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu", "--no-extra", "--streams", "1", "--steps", "20", "--warmup", "3"] + args,
+            out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu", "--no-extra", "--streams", "1", "--steps", "20", "--warmup", "3"] + args,
                                  env=dict(os.environ, CRTHIP_SIG_PAD=pad), stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, timeout=300).stdout.decode()
             try:
                 j = json.loads(out.strip().splitlines()[-1])
