@@ -100,6 +100,19 @@ extern "C" {
 #define CRTHIP_F_VHS_EP       0x4000  /*   other two tape speeds                                                            */
 #define CRTHIP_F_EQ_FIR(taps)  ((taps) << 8)
 #define CRTHIP_F_EQ_FIR_MASK   (7 << 8)
+/* Display modes of the reference's real-time driver, whose displaycb (crt_main.c:454-463) treats the output buffer D before
+ * every field: fadephos on (the default, crt_main.c:308) fades the phosphors, fadephos off clears the display (:462).  One
+ * display step is then  D <- fade(D) (or 0);  crt_modulate;  crt_demodulate onto D  -- with blend the decoder blends against the
+ * faded picture.  Neither flag = D carried over unchanged (extra/video_convert.c), the default.
+ *   fade(c) = (c>>1) + (c>>2) + (c>>3) + (c>>4) on every colour byte (crt_main.c:446-450 on the little-endian word); the alpha
+ *   byte of the 4-byte formats -- the one the decoder writes 0xff into, crt_core.c:620-652: byte 3 of RGBA / BGRA, byte 0 of
+ *   ARGB / ABGR -- becomes 0; RGB / BGR fade all three bytes.  fade is monotone, fade(c) < c for c > 0, fade^38(c) = 0 for every
+ *   byte (and fade^37(255) != 0); clear = every byte 0 = fade applied 38 times or more (crthip_phosphor_table).
+ * crthip_sequence / crthip_seq_weave: image k = D after field k (one display step per field).  crthip_fieldpass: every image of
+ * d_out is its own display, one display step per call.  The stage-level entry points (crthip_modulate / _noise / _sync /
+ * _decode) refuse both flags: there the host owns the buffer, as crt_main.c does.  crthip_params_finalize refuses both at once. */
+#define CRTHIP_F_PHOSPHOR_FADE  0x8000
+#define CRTHIP_F_PHOSPHOR_CLEAR 0x10000
 
 /*
  * Everything that is uniform over a batch of field-passes.  Plain old data, no
@@ -211,6 +224,9 @@ int  crthip_hres(int system, int chroma_pattern);            /* CRT_HRES       *
 int  crthip_lines(int system);                               /* CRT_LINES      */
 size_t crthip_field_stride(int system, int chroma_pattern);  /* bytes between consecutive
                                    fields in analog[] / inp[] device buffers (>= INPUT_SIZE+CRTHIP_TAIL) */
+/* lut[c] = fade^age(c) of a colour byte (CRTHIP_F_PHOSPHOR_FADE, crt_main.c:446-450): lut[c] = c for age 0, all zeros from
+ * age 38 on; CRTHIP_E_ARG for age < 0.  The table the sequence weave applies to a row that is `age` fields old. */
+int  crthip_phosphor_table(int age, unsigned char lut[256]);
 
 /* VHS only.  The reference's VHS noise is the C library's rand() stream (crt_core.c:344-351); on
  * glibc that is y[n] = y[n-31] + y[n-3], rand() = y[n] >> 1.  The kernels take the generator state

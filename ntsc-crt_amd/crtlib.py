@@ -20,6 +20,9 @@ SYSTEM_NTSC, SYSTEM_NES, SYSTEM_PV1K, SYSTEM_SNES, SYSTEM_TEMP, SYSTEM_VHS, SYST
 FMT_RGB, FMT_BGR, FMT_ARGB, FMT_RGBA, FMT_ABGR, FMT_BGRA = range(6)
 F_NES_SETUP, F_VHS_DRAW_ABERRATION, F_BLOOM, F_IMAGE_SPARE_ROW = 2, 4, 8, 16
 F_NO_HSYNC, F_NO_VSYNC, F_VHS_LCG_NOISE, F_HIPASS, F_VHS_LP, F_VHS_EP, F_NES_BORDER = 0x20, 0x40, 0x80, 0x800, 0x2000, 0x4000, 0x1000
+# display modes of crt_main.c's displaycb (crt_main.c:459-463): fade the phosphors / clear the display before every field
+F_PHOSPHOR_FADE, F_PHOSPHOR_CLEAR = 0x8000, 0x10000
+PHOSPHOR_FLAGS = {"keep": 0, "fade": F_PHOSPHOR_FADE, "clear": F_PHOSPHOR_CLEAR}
 K_NAMES = ("template", "active", "noise", "sync", "decode")
 MAX_VPER, MAX_CCS, CARRIER_ROWS = 5, 5, 10
 STATE_INTS = 36      # sizeof(crthip_state) / 4
@@ -137,6 +140,7 @@ def load_library():
     L.crthip_seq_weave.argtypes = [vp, PP, ci, vp, sz, vp, ci]
     L.crthip_set_pixel_tile.argtypes = [vp, ci]
     L.crthip_profile_read.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(ci)]
+    L.crthip_phosphor_table.argtypes = [ci, C.POINTER(C.c_ubyte)]
     _LIB = L
     return L
 
@@ -162,6 +166,15 @@ def make_params(system="ntsc", **kw):
     if rc:
         raise ValueError("crthip_params_finalize failed (%d)" % rc)
     return p
+
+
+def phosphor_table(age):
+    """crthip_phosphor_table (host only): [fade^age(c) for c in 0..255] as bytes, crt_main.c:446-450 per colour byte."""
+    lut = (C.c_ubyte * 256)()
+    rc = load_library().crthip_phosphor_table(int(age), lut)
+    if rc:
+        raise ValueError("crthip_phosphor_table failed (%d)" % rc)
+    return bytes(lut)
 
 
 class Settings:
@@ -214,6 +227,9 @@ class CRT:
         self.scanlines = self.blend = 0
         self.v_fac = 0
         self.eq_fir = 0        # 0: the 3-band equaliser; 7/6/5/4: FIR kernel of a USE_CONVOLUTION build (crt_core.c:85-147)
+        # what happens to the output buffer before every field: "keep" (extra/video_convert.c), "fade" the phosphors or "clear"
+        # the display (crt_main.c:459-463).  fieldpass(): one display step per image and call; sequence() / seq_*: one per field
+        self.phosphor = "keep"
         bpp = bpp4fmt(out_format) or 4
         self.out = out if out is not None else torch.zeros((n, outh, outw, bpp), dtype=torch.uint8, device=self.dev)
         self.state = torch.zeros((n, STATE_INTS), dtype=torch.int32, device=self.dev)
@@ -285,6 +301,9 @@ class CRT:
         else:
             h, w = int(d.shape[1]), int(d.shape[2])
         flags = self.eq_fir << 8                                   # CRTHIP_F_EQ_FIR(taps)
+        if self.phosphor not in PHOSPHOR_FLAGS:
+            raise ValueError("CRT.phosphor must be one of %s, not %r" % (sorted(PHOSPHOR_FLAGS), self.phosphor))
+        flags |= PHOSPHOR_FLAGS[self.phosphor]
         if getattr(s, "draw_aberration", 0):
             flags |= F_VHS_DRAW_ABERRATION                         # sequence mode
         if self._has_spare_row(s):

@@ -80,10 +80,27 @@ __global__ void k_seq_latest(int n_fields, int outh, const unsigned char *owner,
     }
 }
 
-/* rows of image k that field k did not write <- the same row of image latest[k][row] (or the initial image) */
+/* Display modes (CRTHIP_F_PHOSPHOR_FADE / _CLEAR, crt_hip.h): what happens to the output buffer before every field.  KEEP = carried
+ * over unchanged (extra/video_convert.c), FADE = crt_main.c:438-451, CLEAR = crt_main.c:462. */
+enum { PH_KEEP = 0, PH_FADE = 1, PH_CLEAR = 2 };
+
+/* fade of four bytes at once, crt_main.c:446-450: per byte (c>>1) + (c>>2) + (c>>3) + (c>>4) <= 236, so no term carries into the
+ * next byte.  The caller clears the alpha byte of the 4-byte formats (alpha_mask). */
+__device__ __forceinline__ unsigned phos_fade4(unsigned w)
+{
+    return ((w >> 1) & 0x7f7f7f7fu) + ((w >> 2) & 0x3f3f3f3fu) + ((w >> 3) & 0x1f1f1f1fu) + ((w >> 4) & 0x0f0f0f0fu);
+}
+__device__ __forceinline__ unsigned phos_fade1(unsigned c) { return (c >> 1) + (c >> 2) + (c >> 3) + (c >> 4); }
+/* byte `o` of a row (rows start on a pixel) is the alpha byte of its pixel */
+__device__ __forceinline__ bool phos_is_alpha(size_t o, unsigned alpha_mask) { return ((alpha_mask >> (8 * (o & 3))) & 0xffu) != 0; }
+
+/* rows of image k that field k did not write <- the same row of image latest[k][row] (or the initial image).
+ * FADE: that row is age = k - latest fields old (k + 1 for the initial image) and gets fade^age, which is uniform over the block:
+ * a loop of `age` word fades (all zeros from CRTHIP_PHOSPHOR_DEPTH on, without reading the source).  CLEAR: zeros. */
+template <int PH>
 __global__ void __launch_bounds__(256)
 k_seq_weave(int n_fields, int outh, size_t pitch, unsigned char *out, size_t ostride, const unsigned char *init,
-            const int *latest, int patch_only)
+            const int *latest, int patch_only, unsigned alpha_mask)
 {
     const int row = blockIdx.x % outh, k = blockIdx.x / outh;
     if (k >= n_fields) return;
@@ -93,14 +110,79 @@ k_seq_weave(int n_fields, int outh, size_t pitch, unsigned char *out, size_t ost
     unsigned char *dst = out + (size_t) k * ostride + (size_t) row * pitch;
     const unsigned char *src = src_k >= 0 ? out + (size_t) src_k * ostride + (size_t) row * pitch
                                           : (init ? init + (size_t) row * pitch : nullptr);
+    const int age = PH == PH_FADE ? (src_k >= 0 ? k - src_k : k + 1) : 0;
+    if (PH == PH_CLEAR || age >= CRTHIP_PHOSPHOR_DEPTH) src = nullptr;
     for (size_t b = (size_t) threadIdx.x * 16; b < pitch; b += 256 * 16) {
         const size_t nb = pitch - b < 16 ? pitch - b : 16;
         if (nb == 16) {
             v4i v = { 0, 0, 0, 0 };
             if (src) v = load16u(src + b);
+            if (PH == PH_FADE && src) {
+                unsigned w0 = (unsigned) v.x, w1 = (unsigned) v.y, w2 = (unsigned) v.z, w3 = (unsigned) v.w;
+                for (int a = 0; a < age; a++) { w0 = phos_fade4(w0); w1 = phos_fade4(w1); w2 = phos_fade4(w2); w3 = phos_fade4(w3); }
+                v.x = (int) (w0 & ~alpha_mask); v.y = (int) (w1 & ~alpha_mask); v.z = (int) (w2 & ~alpha_mask); v.w = (int) (w3 & ~alpha_mask);
+            }
             store16u(dst + b, v);
         } else {
-            for (size_t c = 0; c < nb; c++) dst[b + c] = src ? src[b + c] : (unsigned char) 0;
+            for (size_t c = 0; c < nb; c++) {
+                unsigned x = src ? src[b + c] : 0u;
+                if (PH == PH_FADE && src) {
+                    for (int a = 0; a < age; a++) x = phos_fade1(x);
+                    if (phos_is_alpha(b + c, alpha_mask)) x = 0;
+                }
+                dst[b + c] = (unsigned char) x;
+            }
+        }
+    }
+}
+
+/* (field-pass) one display step of FADE / CLEAR on every image of the batch, each its own display, before the decoder writes
+ * field k into it: ALL (blend) treats every row -- the decoder then blends against the faded picture --, otherwise only the rows
+ * field k does not write (beg .. beg + nrows - 1 of its line table, clipped to outh, as k_seq_rows), which the decoder leaves alone.
+ * A block = PHOS_ROWS rows of one field, one wave per row at a time; the block's row ownership is a bitmap in LDS built from the
+ * field's line table (no workspace: a field-pass stays allocation-free and graph-capturable). */
+constexpr int PHOS_ROWS = 64;
+template <int PH, bool ALL>
+__global__ void __launch_bounds__(256)
+k_phosphor_rows(int n_fields, int lines_per_field, int outh, int row_blocks, size_t pitch, unsigned char *out, size_t ostride,
+                const crthip_line *lines, unsigned alpha_mask)
+{
+    __shared__ unsigned own[PHOS_ROWS / 32];
+    const int k = (int) (blockIdx.x / (unsigned) row_blocks), r0 = (int) (blockIdx.x % (unsigned) row_blocks) * PHOS_ROWS;
+    if (k >= n_fields) return;
+    const int r1 = r0 + PHOS_ROWS < outh ? r0 + PHOS_ROWS : outh;
+    if (!ALL) {
+        if (threadIdx.x < PHOS_ROWS / 32) own[threadIdx.x] = 0u;
+        __syncthreads();
+        const crthip_line *lf = lines + (size_t) k * lines_per_field;
+        for (int i = threadIdx.x; i < lines_per_field; i += 256) {
+            const int beg = lf[i].beg, nr = lf[i].nrows & CRTHIP_LINE_NROWS_MASK;
+            const int lo = beg > r0 ? beg : r0, hi = beg + nr < r1 ? beg + nr : r1;
+            for (int r = lo; r < hi; r++) atomicOr(&own[(r - r0) >> 5], 1u << ((r - r0) & 31));
+        }
+        __syncthreads();
+    }
+    const int wave = (int) (threadIdx.x >> 6), lane = (int) (threadIdx.x & 63);
+    for (int r = r0 + wave; r < r1; r += 4) {
+        if (!ALL && ((own[(r - r0) >> 5] >> ((r - r0) & 31)) & 1u)) continue;
+        unsigned char *dst = out + (size_t) k * ostride + (size_t) r * pitch;
+        for (size_t b = (size_t) lane * 16; b < pitch; b += 64 * 16) {
+            const size_t nb = pitch - b < 16 ? pitch - b : 16;
+            if (nb == 16) {
+                v4i v = { 0, 0, 0, 0 };
+                if (PH == PH_FADE) {
+                    v = load16u(dst + b);
+                    v.x = (int) (phos_fade4((unsigned) v.x) & ~alpha_mask); v.y = (int) (phos_fade4((unsigned) v.y) & ~alpha_mask);
+                    v.z = (int) (phos_fade4((unsigned) v.z) & ~alpha_mask); v.w = (int) (phos_fade4((unsigned) v.w) & ~alpha_mask);
+                }
+                store16u(dst + b, v);
+            } else {
+                for (size_t c = 0; c < nb; c++) {
+                    unsigned x = 0u;
+                    if (PH == PH_FADE && !phos_is_alpha(b + c, alpha_mask)) x = phos_fade1(dst[b + c]);
+                    dst[b + c] = (unsigned char) x;
+                }
+            }
         }
     }
 }
@@ -123,6 +205,9 @@ __global__ void k_seq_rowsrc(int n_fields, int lines_per_field, int outh, const 
     }
 }
 
+/* FADE: the old word is faded in registers first (the picture the decoder blends against is the faded one, and rows field k
+ * does not write become fade(prev)); CLEAR: the old picture is all zeros and is not read */
+template <int PH>
 __global__ void __launch_bounds__(256)
 k_seq_blend_step(int k, int outh, size_t pitch, unsigned char *out, size_t ostride, const unsigned char *init,
                  const int *rowsrc, unsigned alpha_mask)
@@ -130,7 +215,7 @@ k_seq_blend_step(int k, int outh, size_t pitch, unsigned char *out, size_t ostri
     const int row = blockIdx.x;
     const int src = rowsrc[(size_t) k * outh + row];
     unsigned char *cur = out + (size_t) k * ostride + (size_t) row * pitch;
-    const unsigned char *prev_img = k ? out + (size_t) (k - 1) * ostride : init;      /* nullptr: zeros (calloc) */
+    const unsigned char *prev_img = PH == PH_CLEAR ? nullptr : (k ? out + (size_t) (k - 1) * ostride : init);   /* nullptr: zeros (calloc) */
     const unsigned char *old = prev_img ? prev_img + (size_t) (src < 0 ? row : src) * pitch : nullptr;
     for (size_t b = (size_t) threadIdx.x * 4; b < pitch; b += 256 * 4) {
         const size_t nb = pitch - b < 4 ? pitch - b : 4;
@@ -139,6 +224,7 @@ k_seq_blend_step(int k, int outh, size_t pitch, unsigned char *out, size_t ostri
             o |= (unsigned) (old ? old[b + c] : 0) << (8 * c);
             n |= (unsigned) cur[b + c] << (8 * c);
         }
+        if (PH == PH_FADE) o = phos_fade4(o) & ~alpha_mask;      /* b is a multiple of 4: the word is one pixel of a 4-byte format */
         /* every colour byte: (new >> 1) + (old >> 1) -- what the 0xfefeff mask computes per channel; alpha stays 0xff */
         const unsigned v = src < 0 ? o : ((((n >> 1) & 0x7f7f7f7fu) + ((o >> 1) & 0x7f7f7f7fu)) | alpha_mask);
         for (size_t c = 0; c < nb; c++) cur[b + c] = (unsigned char) (v >> (8 * c));
@@ -216,6 +302,33 @@ static bool layout_rule(int system, int pattern, const struct crt_sysdef &sd, si
 bool crt_fused_layout(const crthip_ctx *c, const crthip_params *p, int n, sig_layout *lay)
 {
     return layout_rule(c->system, c->pattern, c->sd, c->fstride, p, n, c->shape, c->sig_pad, lay);
+}
+
+/* the byte the decoder writes 0xff into (crt_core.c:620-652): byte 3 of RGBA / BGRA, byte 0 of ARGB / ABGR, none for RGB / BGR */
+static unsigned out_alpha_mask(const crthip_params *p)
+{
+    const int fmt = p->out_format;
+    return p->out_bpp == 3 ? 0u : ((fmt == CRTHIP_FMT_ARGB || fmt == CRTHIP_FMT_ABGR) ? 0x000000ffu : 0xff000000u);
+}
+
+static int phosphor_mode(const crthip_params *p)
+{
+    return (p->flags & CRTHIP_F_PHOSPHOR_FADE) ? PH_FADE : (p->flags & CRTHIP_F_PHOSPHOR_CLEAR) ? PH_CLEAR : PH_KEEP;
+}
+
+/* a field-pass's display step on fields [0, n) of `out` (their line tables at `ln`), before their decoder runs */
+template <int PH>
+static void launch_phosphor_rows(crthip_ctx *c, const crthip_params *p, int n, const crthip_line *ln, unsigned char *out, size_t ostride)
+{
+    const int rb = (p->outh + PHOS_ROWS - 1) / PHOS_ROWS;
+    const size_t pitch = (size_t) p->outw * p->out_bpp;
+    const dim3 grid((unsigned) n * (unsigned) rb);
+    if (p->blend)
+        hipLaunchKernelGGL((k_phosphor_rows<PH, true>), grid, dim3(256), 0, c->stream, n, c->sd.lines, p->outh, rb, pitch, out, ostride, ln,
+                           out_alpha_mask(p));
+    else
+        hipLaunchKernelGGL((k_phosphor_rows<PH, false>), grid, dim3(256), 0, c->stream, n, c->sd.lines, p->outh, rb, pitch, out, ostride, ln,
+                           out_alpha_mask(p));
 }
 
 extern "C" {
@@ -447,6 +560,16 @@ static int check_params(crthip_ctx *c, const crthip_params *p, int n)
     return CRTHIP_OK;
 }
 
+/* the stage-level entry points: the host owns the output buffer between the stages (crt_main.c:459-463 fades it itself) */
+static int check_stage_params(crthip_ctx *c, const crthip_params *p, int n)
+{
+    const int rc = check_params(c, p, n);
+    if (rc) return rc;
+    if (p->flags & CRTHIP_PHOSPHOR_MASK)
+        return set_err(c, CRTHIP_E_ARG, "phosphor fade / clear: only crthip_fieldpass and the sequence entry points own the output buffer", hipSuccess);
+    return CRTHIP_OK;
+}
+
 /* The encoder contract.  The reference writes analog[(x + xo) + (y + yo) * HRES] (crt_ntsc.c:322) -- a FLAT index:
  * a rectangle that runs over the end of a line (xoffset = 4 in standard NTSC: 160 + 753 > 910) simply continues in
  * the next line's front porch, and the kernels do exactly the same (they work on flat indices too).  What is refused
@@ -466,7 +589,7 @@ static int check_encoder(crthip_ctx *c, const crthip_params *p)
 int crthip_modulate(crthip_ctx *c, const crthip_params *p, int n, const void *d_images, size_t istride,
                     signed char *d_analog, crthip_state *d_state)
 {
-    int rc = check_params(c, p, n);
+    int rc = check_stage_params(c, p, n);
     if (rc) return rc;
     rc = check_encoder(c, p);
     if (rc) return rc < 0 ? rc : CRTHIP_OK;
@@ -482,7 +605,7 @@ int crthip_modulate(crthip_ctx *c, const crthip_params *p, int n, const void *d_
 int crthip_noise(crthip_ctx *c, const crthip_params *p, int n, const signed char *d_analog, signed char *d_inp,
                  crthip_state *d_state)
 {
-    int rc = check_params(c, p, n);
+    int rc = check_stage_params(c, p, n);
     if (rc) return rc;
     if (p->out_bpp == 0) return CRTHIP_OK;                       /* crt_core.c:312-315 */
     if (!d_analog || !d_inp || !d_state) return CRTHIP_E_ARG;
@@ -499,7 +622,7 @@ int crthip_noise(crthip_ctx *c, const crthip_params *p, int n, const signed char
 int crthip_sync(crthip_ctx *c, const crthip_params *p, int n, const signed char *d_inp, crthip_state *d_state,
                 crthip_line *d_lines)
 {
-    int rc = check_params(c, p, n);
+    int rc = check_stage_params(c, p, n);
     if (rc) return rc;
     if (p->out_bpp == 0) return CRTHIP_OK;
     if (!d_inp || !d_state || !d_lines) return CRTHIP_E_ARG;
@@ -512,7 +635,7 @@ int crthip_sync(crthip_ctx *c, const crthip_params *p, int n, const signed char 
 int crthip_decode(crthip_ctx *c, const crthip_params *p, int n, const signed char *d_inp, const crthip_line *d_lines,
                   void *d_out, size_t ostride)
 {
-    int rc = check_params(c, p, n);
+    int rc = check_stage_params(c, p, n);
     if (rc) return rc;
     if (p->out_bpp == 0) return CRTHIP_OK;
     if (!d_inp || !d_lines || !d_out) return CRTHIP_E_ARG;
@@ -567,7 +690,9 @@ static int fieldpass_chunk(crthip_ctx *c, const crthip_params *p, int enc, int f
             if (p->out_bpp == 0) return CRTHIP_OK;
             unsigned *saved = c->d_vhs_hist;
             if (vhs_rand) c->d_vhs_hist = saved + (size_t) first * 32;
-            rc = crthip_noise(c, p, n, analog, inp, st);
+            crthip_params pn = *p;
+            pn.flags &= ~CRTHIP_PHOSPHOR_MASK;            /* the display step belongs to the decoder part below */
+            rc = crthip_noise(c, &pn, n, analog, inp, st);
             c->d_vhs_hist = saved;
             if (rc) return rc;
             rc = crt_run_sync(c, p, n, inp, st, ln, 0);
@@ -593,7 +718,12 @@ static int fieldpass_chunk(crthip_ctx *c, const crthip_params *p, int enc, int f
         rc = crt_run_sync(c, &q, n, inp, st, ln, 1, preset ? 1 : 0, &lay);
         if (rc) return rc;
     }
-    if ((part & 2) && p->out_bpp != 0) rc = crt_run_decode(c, p, n, inp, ln, out, ostride, lay.fstride);
+    if ((part & 2) && p->out_bpp != 0) {
+        /* CRTHIP_F_PHOSPHOR_*: displaycb's fade / clear (crt_main.c:459-463) between the sync chain and the decoder */
+        if (phosphor_mode(p) == PH_FADE) launch_phosphor_rows<PH_FADE>(c, p, n, ln, out, ostride);
+        else if (phosphor_mode(p) == PH_CLEAR) launch_phosphor_rows<PH_CLEAR>(c, p, n, ln, out, ostride);
+        rc = crt_run_decode(c, p, n, inp, ln, out, ostride, lay.fstride);
+    }
     return rc;
 }
 
@@ -897,14 +1027,22 @@ int crthip_seq_weave(crthip_ctx *c, const crthip_params *p, int n, void *d_out, 
     if (rc) return rc;
     const int outh = p->outh;
     const size_t pitch = (size_t) p->outw * p->out_bpp;
+    const unsigned alpha = out_alpha_mask(p);
+    const int ph = phosphor_mode(p);
     if (p->blend) {
         HIPCHK(c, hipMemsetAsync(sc.latest, 0xff, sizeof(int) * (size_t) n * outh, c->stream));       /* -1 everywhere */
         hipLaunchKernelGGL(k_seq_rowsrc, dim3((n * c->sd.lines + 255) / 256), dim3(256), 0, c->stream, n, c->sd.lines, outh, c->d_lines, sc.latest);
-        const int fmt = p->out_format;
-        const unsigned alpha = p->out_bpp == 3 ? 0u : ((fmt == CRTHIP_FMT_ARGB || fmt == CRTHIP_FMT_ABGR) ? 0x000000ffu : 0xff000000u);
-        for (int k = 0; k < n; k++)
-            hipLaunchKernelGGL(k_seq_blend_step, dim3((unsigned) outh), dim3(256), 0, c->stream, k, outh, pitch,
-                               (unsigned char *) d_out, ostride, (const unsigned char *) d_out_init, sc.latest, alpha);
+        for (int k = 0; k < n; k++) {
+            if (ph == PH_FADE)
+                hipLaunchKernelGGL(k_seq_blend_step<PH_FADE>, dim3((unsigned) outh), dim3(256), 0, c->stream, k, outh, pitch,
+                                   (unsigned char *) d_out, ostride, (const unsigned char *) d_out_init, sc.latest, alpha);
+            else if (ph == PH_CLEAR)
+                hipLaunchKernelGGL(k_seq_blend_step<PH_CLEAR>, dim3((unsigned) outh), dim3(256), 0, c->stream, k, outh, pitch,
+                                   (unsigned char *) d_out, ostride, (const unsigned char *) d_out_init, sc.latest, alpha);
+            else
+                hipLaunchKernelGGL(k_seq_blend_step<PH_KEEP>, dim3((unsigned) outh), dim3(256), 0, c->stream, k, outh, pitch,
+                                   (unsigned char *) d_out, ostride, (const unsigned char *) d_out_init, sc.latest, alpha);
+        }
         HIPCHK(c, hipGetLastError());
         return CRTHIP_OK;
     }
@@ -913,8 +1051,16 @@ int crthip_seq_weave(crthip_ctx *c, const crthip_params *p, int n, void *d_out, 
         hipLaunchKernelGGL(k_seq_rows, dim3((n * c->sd.lines + 255) / 256), dim3(256), 0, c->stream, n, c->sd.lines, outh, c->d_lines, sc.owner);
         hipLaunchKernelGGL(k_seq_latest, dim3((outh + 63) / 64), dim3(64), 0, c->stream, n, outh, sc.owner, sc.latest);
     }
-    hipLaunchKernelGGL(k_seq_weave, dim3((unsigned) n * (unsigned) outh), dim3(256), 0, c->stream, n, outh, pitch,
-                       (unsigned char *) d_out, ostride, (const unsigned char *) d_out_init, sc.latest, patch_only);
+    const dim3 grid((unsigned) n * (unsigned) outh);
+    if (ph == PH_FADE)
+        hipLaunchKernelGGL(k_seq_weave<PH_FADE>, grid, dim3(256), 0, c->stream, n, outh, pitch,
+                           (unsigned char *) d_out, ostride, (const unsigned char *) d_out_init, sc.latest, patch_only, alpha);
+    else if (ph == PH_CLEAR)
+        hipLaunchKernelGGL(k_seq_weave<PH_CLEAR>, grid, dim3(256), 0, c->stream, n, outh, pitch,
+                           (unsigned char *) d_out, ostride, (const unsigned char *) d_out_init, sc.latest, patch_only, alpha);
+    else
+        hipLaunchKernelGGL(k_seq_weave<PH_KEEP>, grid, dim3(256), 0, c->stream, n, outh, pitch,
+                           (unsigned char *) d_out, ostride, (const unsigned char *) d_out_init, sc.latest, patch_only, alpha);
     HIPCHK(c, hipGetLastError());
     return CRTHIP_OK;
 }

@@ -356,6 +356,25 @@ lowpass_coef(int limit)
     return Q11 - crt_setup_expx(-((6434 << 9) / rate));
 }
 
+/* fade^age of every byte value (crt_main.c:446-450 per byte: the four shifted terms never carry into the next byte) */
+int
+crthip_phosphor_table(int age, unsigned char lut[256])
+{
+    int c, a;
+
+    if (age < 0 || lut == 0) {
+        return CRTHIP_E_ARG;
+    }
+    for (c = 0; c < 256; c++) {
+        unsigned v = (unsigned) c;
+        for (a = 0; a < age && v != 0; a++) {
+            v = (v >> 1) + (v >> 2) + (v >> 3) + (v >> 4);
+        }
+        lut[c] = (unsigned char) v;
+    }
+    return CRTHIP_OK;
+}
+
 int
 crthip_params_finalize(crthip_params *p)
 {
@@ -394,6 +413,9 @@ crthip_params_finalize(crthip_params *p)
     }
     if ((p->flags & CRTHIP_F_NES_BORDER) && p->system != CRTHIP_SYSTEM_NES) {
         return CRTHIP_E_ARG;
+    }
+    if ((p->flags & CRTHIP_F_PHOSPHOR_FADE) && (p->flags & CRTHIP_F_PHOSPHOR_CLEAR)) {
+        return CRTHIP_E_ARG;                                    /* crt_main.c:459-463: fade or clear, never both */
     }
 
     memset(p->burst, 0, sizeof(p->burst));

@@ -57,6 +57,10 @@ void crt_setup_vhs_power_table(unsigned long first, unsigned long step, int coun
 
 #define CRTHIP_PARAMS_MAGIC 0x43525431            /* "CRT1" */
 
+/* CRTHIP_F_PHOSPHOR_FADE / _CLEAR (crt_hip.h): fade^CRTHIP_PHOSPHOR_DEPTH(c) == 0 for every byte c, fade^(DEPTH-1)(255) != 0 */
+#define CRTHIP_PHOSPHOR_MASK  (CRTHIP_F_PHOSPHOR_FADE | CRTHIP_F_PHOSPHOR_CLEAR)
+#define CRTHIP_PHOSPHOR_DEPTH 38
+
 #ifdef __cplusplus
 }
 #endif
