@@ -292,6 +292,29 @@ int  crthip_sequence(crthip_ctx *ctx, const crthip_params *p, int n,
                      crthip_state *d_state, int *passes);
 
 /*
+ * Sequence mode for MANY television sets in one call: n_sets independent sets, set s = the consecutive fields
+ * [set_first[s], set_first[s + 1]) of the batch (set_first: a HOST array of n_sets + 1 entries, set_first[0] == 0, strictly
+ * ascending -- every set has at least one field; n = set_first[n_sets] fields in all; the sets may differ in length).  Byte for
+ * byte and state for state what crthip_sequence gives when called once per set on the set's slice of d_images, d_out and
+ * d_state -- with or without blend, with the phosphor flags, every system and kernel shape -- at ONE launch sequence: the number
+ * of kernel launches and host synchronisations of a call does not depend on n_sets, and on n only through the sync passes.
+ *   d_state[k].field / .frame / .aux : encoder inputs of field k;  d_state[set_first[s]].hsync / .vsync / .rn : set s's state
+ *   before its first field, read ON THE DEVICE (no state travels through the host); on return d_state[k] = the state after field k.
+ *   d_out_init + s * out_init_stride = set s's output buffer before its first field; out_init_stride == 0: one picture shared
+ *   by all sets; d_out_init == NULL: zeros.
+ *   *passes (optional) = passes of the joint sync fixed point (one pass covers all sets; at most the longest set's length + 1).
+ * Refused (CRTHIP_E_ARG, crthip_error_string says why): anything else in set_first; what crthip_sequence refuses; the VHS build
+ * with rand() noise (CRTHIP_SYSTEM_NTSCVHS without CRTHIP_F_VHS_LCG_NOISE: every set would own a rand() stream) and
+ * CRTHIP_F_VHS_DRAW_ABERRATION, which draws from that stream (give the aberration heights in d_state[k].aux).
+ */
+int  crthip_sequence_sets(crthip_ctx *ctx, const crthip_params *p,
+                          int n_sets, const int *set_first,
+                          const void *d_images, size_t image_stride,
+                          void *d_out, size_t out_stride,
+                          const void *d_out_init, size_t out_init_stride,
+                          crthip_state *d_state, int *passes);
+
+/*
  * The phases of crthip_sequence, for hosts that cut ONE video over several contexts / devices / processes
  * (include/crt_hip_node.h; ntsc-crt_amd/shard.py over torch.distributed).  A shard holds the n consecutive fields
  * [first_index, first_index + n) of the video; crthip_sequence == encode(0, rn0) + sync + decode + weave on one context.

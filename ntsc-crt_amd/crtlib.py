@@ -132,6 +132,7 @@ def load_library():
     L.crthip_table_generation.argtypes = [vp]
     L.crthip_table_generation.restype = C.c_uint
     L.crthip_sequence.argtypes = [vp, PP, ci, vp, sz, vp, sz, vp, vp, C.POINTER(ci)]
+    L.crthip_sequence_sets.argtypes = [vp, PP, ci, C.POINTER(ci), vp, sz, vp, sz, vp, sz, vp, C.POINTER(ci)]
     L.crthip_vhs_chain.argtypes = [vp, ci, vp, ci]
     L.crthip_seq_vhs_prechained.argtypes = [vp, ci]
     L.crthip_seq_encode.argtypes = [vp, PP, ci, ci, ci, vp, sz, vp]
@@ -398,6 +399,34 @@ class CRT:
                                     C.c_void_p(out_init.data_ptr()) if out_init is not None else None,
                                     C.c_void_p(self.state.data_ptr()), C.byref(passes))
         self._check(rc, "crthip_sequence")
+        s.initialized = 1
+        return passes.value
+
+    def sequence_sets(self, s, noise, set_first, out_init=None):
+        """Many television sets in one call: set i = the consecutive fields [set_first[i], set_first[i + 1]) of the batch
+        (``set_first``: n_sets + 1 ints from 0 to n, strictly ascending), each processed as ``sequence`` would process it alone.
+        ``self.state[set_first[i]]`` holds set i's hsync / vsync / rn before its first field; ``out_init``: None (zeros), one
+        picture [outh, outw, bpp] shared by all sets, or [n_sets, outh, outw, bpp]; returns the passes of the joint sync fixed point."""
+        first = [int(v) for v in set_first]
+        n_sets = len(first) - 1
+        if n_sets < 1 or first[-1] != self.n:
+            raise ValueError("set_first must run from 0 to the batch size %d in n_sets + 1 entries" % self.n)
+        init_ptr, init_stride = None, 0
+        if out_init is not None:
+            assert out_init.is_contiguous() and out_init.device == self.dev and out_init.dtype == self.torch.uint8
+            if out_init.dim() == 4:
+                if int(out_init.shape[0]) != n_sets:
+                    raise ValueError("out_init holds %d pictures for %d sets" % (int(out_init.shape[0]), n_sets))
+                init_stride = out_init.stride(0)
+            init_ptr = C.c_void_p(out_init.data_ptr())
+        p = self.params(s, noise)
+        self._load_field_state(s)
+        passes = C.c_int(0)
+        rc = self.L.crthip_sequence_sets(self.ctx, C.byref(p), n_sets, (C.c_int * (n_sets + 1))(*first),
+                                         C.c_void_p(s.data.data_ptr()), self._image_stride(s),
+                                         C.c_void_p(self.out.data_ptr()), self.out.stride(0), init_ptr, init_stride,
+                                         C.c_void_p(self.state.data_ptr()), C.byref(passes))
+        self._check(rc, "crthip_sequence_sets")
         s.initialized = 1
         return passes.value
 

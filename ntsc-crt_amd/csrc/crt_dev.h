@@ -539,6 +539,8 @@ struct crthip_ctx {
     size_t bloom_cap;
     unsigned char *d_seq;       /* crthip_sequence scratch */
     size_t seq_cap;
+    int *seq_sets_host;         /* crthip_sequence_sets: host copy of the set table while its upload is in flight */
+    size_t seq_sets_host_cap;
     bool vhs_prechained;        /* crthip_seq_vhs_prechained: the bound histories already sit at the start of every field */
     int seq_guess_n;            /* crthip_seq_sync: the guess array holds the finals of a previous call for this many fields (warm restart) */
     unsigned *d_vhs_rows;       /* VHS: jump coefficients, (vhs_chunks + 1) x 31 words, then 31 x 64 (tail blocks) */

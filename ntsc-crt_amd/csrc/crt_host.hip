@@ -231,6 +231,206 @@ k_seq_blend_step(int k, int outh, size_t pitch, unsigned char *out, size_t ostri
     }
 }
 
+/* ------------------------------------------------------------------------- */
+/* Sequence mode for MANY sets in one call (crthip_sequence_sets)               */
+/* ------------------------------------------------------------------------- */
+/* n_sets independent television sets, set s = the consecutive fields [set_first[s], set_first[s + 1]) of the batch.  The encoder,
+ * sync and decoder kernels run over all fields as above; the small kernels around them learn where a set begins from a per-field
+ * table tab[k] = (first field of k's set, index of the set).  Nothing of a set's state ever travels through the host. */
+
+/* inc[s] = (hsync, vsync, rn) of set s before its first field, taken before anything writes the states */
+__global__ void k_sets_incoming(int n_sets, const int *set_first, const crthip_state *state, int4 *inc)
+{
+    const int s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= n_sets) return;
+    const crthip_state *st = state + set_first[s];
+    inc[s] = make_int4(st->hsync, st->vsync, st->rn, 0);
+}
+
+/* state[k].rn = J^(k - first)(the set's incoming rn) as k_seq_rn; guess[k] = the set's incoming pair ("nobody's sync state moves") */
+__global__ void k_sets_rn(int n_fields, crthip_state *state, const int2 *tab, const int4 *inc, int2 *guess, uint2 whole_field)
+{
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n_fields) return;
+    const int2 t = tab[k];
+    const int4 in = inc[t.y];
+    unsigned pm = whole_field.x, pa = whole_field.y, m = 1u, a = 0u;
+    for (unsigned e = (unsigned) (k - t.x); e; e >>= 1) {
+        if (e & 1u) { m = pm * m; a = pm * a + pa; }
+        pa = pm * pa + pa;
+        pm = pm * pm;
+    }
+    state[k].rn = (int) (m * (unsigned) in.z + a);
+    guess[k] = make_int2(in.x, in.y);
+}
+
+/* init_k = the set's incoming pair for the first field of a set, guess[k-1] otherwise */
+__global__ void k_sets_load(int n_fields, crthip_state *state, const int2 *tab, const int4 *inc, const int2 *guess)
+{
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n_fields) return;
+    const int2 t = tab[k];
+    int2 v;
+    if (k == t.x) { const int4 in = inc[t.y]; v = make_int2(in.x, in.y); }
+    else v = guess[k - 1];
+    state[k].hsync = v.x;
+    state[k].vsync = v.y;
+}
+
+/* latest[k][row] = last field of k's set, <= k, that wrote the row (an absolute field index), -1 = none: one lane per (set, row) */
+__global__ void k_sets_latest(int n_sets, int outh, const int *set_first, const unsigned char *owner, int *latest)
+{
+    const int gid = blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid >= n_sets * outh) return;
+    const int s = gid / outh, r = gid - s * outh;
+    int last = -1;
+    for (int k = set_first[s]; k < set_first[s + 1]; k++) {
+        if (owner[(size_t) k * outh + r]) last = k;
+        latest[(size_t) k * outh + r] = last;
+    }
+}
+
+/* k_seq_weave with the set boundary: the initial picture is the one of the field's own set, and it is k - first + 1 fields old */
+template <int PH>
+__global__ void __launch_bounds__(256)
+k_sets_weave(int n_fields, int outh, size_t pitch, unsigned char *out, size_t ostride, const unsigned char *init, size_t init_stride,
+             const int2 *tab, const int *latest, unsigned alpha_mask)
+{
+    const int row = blockIdx.x % outh, k = blockIdx.x / outh;
+    if (k >= n_fields) return;
+    const int src_k = latest[(size_t) k * outh + row];
+    if (src_k == k) return;
+    const int2 t = tab[k];
+    unsigned char *dst = out + (size_t) k * ostride + (size_t) row * pitch;
+    const unsigned char *src = src_k >= 0 ? out + (size_t) src_k * ostride + (size_t) row * pitch
+                                          : (init ? init + (size_t) t.y * init_stride + (size_t) row * pitch : nullptr);
+    const int age = PH == PH_FADE ? (src_k >= 0 ? k - src_k : k - t.x + 1) : 0;
+    if (PH == PH_CLEAR || age >= CRTHIP_PHOSPHOR_DEPTH) src = nullptr;
+    for (size_t b = (size_t) threadIdx.x * 16; b < pitch; b += 256 * 16) {
+        const size_t nb = pitch - b < 16 ? pitch - b : 16;
+        if (nb == 16) {
+            v4i v = { 0, 0, 0, 0 };
+            if (src) v = load16u(src + b);
+            if (PH == PH_FADE && src) {
+                unsigned w0 = (unsigned) v.x, w1 = (unsigned) v.y, w2 = (unsigned) v.z, w3 = (unsigned) v.w;
+                for (int a = 0; a < age; a++) { w0 = phos_fade4(w0); w1 = phos_fade4(w1); w2 = phos_fade4(w2); w3 = phos_fade4(w3); }
+                v.x = (int) (w0 & ~alpha_mask); v.y = (int) (w1 & ~alpha_mask); v.z = (int) (w2 & ~alpha_mask); v.w = (int) (w3 & ~alpha_mask);
+            }
+            store16u(dst + b, v);
+        } else {
+            for (size_t c = 0; c < nb; c++) {
+                unsigned x = src ? src[b + c] : 0u;
+                if (PH == PH_FADE && src) {
+                    for (int a = 0; a < age; a++) x = phos_fade1(x);
+                    if (phos_is_alpha(b + c, alpha_mask)) x = 0;
+                }
+                dst[b + c] = (unsigned char) x;
+            }
+        }
+    }
+}
+
+/* 16 bytes of a row, or the nb < 16 that are left of it (zero filled) */
+__device__ __forceinline__ v4i strip_load(const unsigned char *p, int nb)
+{
+    if (nb == 16) return load16u(p);
+    unsigned w[4] = { 0u, 0u, 0u, 0u };
+    for (int c = 0; c < nb; c++) w[c >> 2] |= (unsigned) p[c] << (8 * (c & 3));
+    v4i v = { (int) w[0], (int) w[1], (int) w[2], (int) w[3] };
+    return v;
+}
+__device__ __forceinline__ void strip_store(unsigned char *p, v4i v, int nb)
+{
+    if (nb == 16) { store16u(p, v); return; }
+    const unsigned w[4] = { (unsigned) v.x, (unsigned) v.y, (unsigned) v.z, (unsigned) v.w };
+    for (int c = 0; c < nb; c++) p[c] = (unsigned char) (w[c >> 2] >> (8 * (c & 3)));
+}
+/* one word of the recurrence of k_seq_blend_step: `o` = the old word (already taken at the row the line started on) */
+template <int PH> __device__ __forceinline__ unsigned fold_word(unsigned n, unsigned o, bool written, unsigned alpha_mask)
+{
+    if (PH == PH_CLEAR) o = 0u;
+    if (PH == PH_FADE) o = phos_fade4(o) & ~alpha_mask;
+    return written ? ((((n >> 1) & 0x7f7f7f7fu) + ((o >> 1) & 0x7f7f7f7fu)) | alpha_mask) : o;
+}
+
+/* blend != 0 for all sets in ONE launch.  The recurrence v_k[row] = src < 0 ? f(v_{k-1}[row]) : blend(new_k[row], f(v_{k-1}[src]))
+ * takes the old value at row src = the first row of the line that wrote `row`, so with duplicated rows a row's chain crosses into
+ * other rows from field to field: rows are not independent -- but byte columns are.  A workgroup owns one set x one strip of 16
+ * bytes of the row (4 pixels of the 4-byte formats; the rows start on a pixel and the strip on a multiple of 4 bytes, so every word
+ * is a pixel and takes alpha_mask; RGB / BGR have mask 0 and the fold is bytewise) over ALL rows, keeps that strip of v_{k-1} in
+ * LDS (two buffers of 16 B x outh, so one barrier per field) and walks its set's fields in order: every image is read once and
+ * written once, and what the workgroup has just stored is never read back through the vector cache.  Work items are dealt so that
+ * the eight strips of a 128-byte line go to workgroups of the same XCD (block_item, crt_dev.h). */
+template <int PH>
+__global__ void __launch_bounds__(256)
+k_sets_fold(int n_items, int order_k, int order_per, int strips, int outh, size_t pitch, unsigned char *out, size_t ostride,
+            const unsigned char *init, size_t init_stride, const int *set_first, const int *rowsrc, unsigned alpha_mask)
+{
+    extern __shared__ v4i fold_lds[];                  /* [2][outh] */
+    const int item = block_item(blockIdx.x, order_k, order_per);
+    if (item >= n_items) return;
+    const int s = item / strips;
+    const size_t b = (size_t) (item - s * strips) * 16;
+    const int nb = pitch - b < 16 ? (int) (pitch - b) : 16;
+    const int k0 = set_first[s], k1 = set_first[s + 1];
+    for (int r = threadIdx.x; r < outh; r += 256) {
+        v4i v = { 0, 0, 0, 0 };
+        if (init && PH != PH_CLEAR) v = strip_load(init + (size_t) s * init_stride + (size_t) r * pitch + b, nb);
+        fold_lds[r] = v;
+    }
+    __syncthreads();
+    int cur = 0;
+    for (int k = k0; k < k1; k++) {
+        unsigned char *img = out + (size_t) k * ostride + b;
+        const int *src_k = rowsrc + (size_t) k * outh;
+        const v4i *old = fold_lds + (size_t) cur * outh;
+        v4i *nxt = fold_lds + (size_t) (cur ^ 1) * outh;
+        for (int r = threadIdx.x; r < outh; r += 256) {
+            const int src = src_k[r];
+            const bool written = src >= 0;
+            v4i n = { 0, 0, 0, 0 };
+            if (written) n = strip_load(img + (size_t) r * pitch, nb);
+            const v4i o = old[written ? src : r];
+            v4i v;
+            v.x = (int) fold_word<PH>((unsigned) n.x, (unsigned) o.x, written, alpha_mask);
+            v.y = (int) fold_word<PH>((unsigned) n.y, (unsigned) o.y, written, alpha_mask);
+            v.z = (int) fold_word<PH>((unsigned) n.z, (unsigned) o.z, written, alpha_mask);
+            v.w = (int) fold_word<PH>((unsigned) n.w, (unsigned) o.w, written, alpha_mask);
+            strip_store(img + (size_t) r * pitch, v, nb);
+            nxt[r] = v;
+        }
+        __syncthreads();
+        cur ^= 1;
+    }
+}
+
+/* the same recurrence where the strips of a picture do not fit the LDS (pictures taller than FOLD_LDS_MAX_ROWS): field j of EVERY set
+ * per launch, a block per (set, row) as k_seq_blend_step -- as many launches as the longest set has fields */
+constexpr int FOLD_LDS_MAX_ROWS = 2048;                /* 2 x 16 B x 2048 rows = the 64 KB of LDS a workgroup may take */
+template <int PH>
+__global__ void __launch_bounds__(256)
+k_sets_blend_step(int j, int outh, size_t pitch, unsigned char *out, size_t ostride, const unsigned char *init, size_t init_stride,
+                  const int *set_first, const int *rowsrc, unsigned alpha_mask)
+{
+    const int row = blockIdx.x % outh, s = blockIdx.x / outh;
+    const int k = set_first[s] + j;
+    if (k >= set_first[s + 1]) return;
+    const int src = rowsrc[(size_t) k * outh + row];
+    unsigned char *cur = out + (size_t) k * ostride + (size_t) row * pitch;
+    const unsigned char *prev_img = PH == PH_CLEAR ? nullptr : (j ? out + (size_t) (k - 1) * ostride : (init ? init + (size_t) s * init_stride : nullptr));
+    const unsigned char *old = prev_img ? prev_img + (size_t) (src < 0 ? row : src) * pitch : nullptr;
+    for (size_t b = (size_t) threadIdx.x * 4; b < pitch; b += 256 * 4) {
+        const int nb = pitch - b < 4 ? (int) (pitch - b) : 4;
+        unsigned o = 0, n = 0;
+        for (int c = 0; c < nb; c++) {
+            o |= (unsigned) (old ? old[b + c] : 0) << (8 * c);
+            n |= (unsigned) cur[b + c] << (8 * c);
+        }
+        const unsigned v = fold_word<PH>(n, o, src >= 0, alpha_mask);
+        for (int c = 0; c < nb; c++) cur[b + c] = (unsigned char) (v >> (8 * c));
+    }
+}
+
 
 /* (r6) the fused path's padded signal (crt_dev.h, sig_layout) back in the reference's flat layout, 16 samples per lane: what
  * crthip_fieldpass_signal hands out (tests compare it with the oracle's inp[] byte for byte; nothing in a field-pass needs it) */
@@ -329,6 +529,30 @@ static void launch_phosphor_rows(crthip_ctx *c, const crthip_params *p, int n, c
     else
         hipLaunchKernelGGL((k_phosphor_rows<PH, false>), grid, dim3(256), 0, c->stream, n, c->sd.lines, p->outh, rb, pitch, out, ostride, ln,
                            out_alpha_mask(p));
+}
+
+/* crthip_sequence_sets: its scratch (sets_scratch below) and the last phase, by display mode */
+struct SetsScratch { int *set_first; int2 *tab; int4 *inc; int2 *guess; int *changed; unsigned char *owner; int *latest; };
+template <int PH>
+static void launch_sets_weave(crthip_ctx *c, const crthip_params *p, int n_sets, int n, int max_len, unsigned char *out, size_t ostride,
+                              const unsigned char *init, size_t init_stride, const SetsScratch &sc)
+{
+    const int outh = p->outh;
+    const size_t pitch = (size_t) p->outw * p->out_bpp;
+    const unsigned alpha = out_alpha_mask(p);
+    if (!p->blend) {
+        hipLaunchKernelGGL((k_sets_weave<PH>), dim3((unsigned) n * (unsigned) outh), dim3(256), 0, c->stream, n, outh, pitch, out, ostride,
+                           init, init_stride, sc.tab, sc.latest, alpha);
+    } else if (outh <= FOLD_LDS_MAX_ROWS) {
+        const int strips = (int) ((pitch + 15) / 16);
+        const block_order o = make_block_order(n_sets * strips, 8);
+        hipLaunchKernelGGL((k_sets_fold<PH>), dim3(o.grid), dim3(256), 2 * sizeof(v4i) * (size_t) outh, c->stream, n_sets * strips, o.K, o.per,
+                           strips, outh, pitch, out, ostride, init, init_stride, sc.set_first, sc.latest, alpha);
+    } else {
+        for (int j = 0; j < max_len; j++)
+            hipLaunchKernelGGL((k_sets_blend_step<PH>), dim3((unsigned) n_sets * (unsigned) outh), dim3(256), 0, c->stream, j, outh, pitch, out,
+                               ostride, init, init_stride, sc.set_first, sc.latest, alpha);
+    }
 }
 
 extern "C" {
@@ -486,6 +710,7 @@ void crthip_destroy(crthip_ctx *c)
     if (c->d_vhs_dig) hipFree(c->d_vhs_dig);
     if (c->d_vhs_next) hipFree(c->d_vhs_next);
     if (c->d_seq) hipFree(c->d_seq);
+    free(c->seq_sets_host);
     if (c->d_bloom) hipFree(c->d_bloom);
     if (c->table_stream) { hipStreamSynchronize(c->table_stream); hipStreamDestroy(c->table_stream); }
     if (c->d_nes_tab) hipFree(c->d_nes_tab);
@@ -1100,6 +1325,136 @@ int crthip_sequence(crthip_ctx *c, const crthip_params *p, int n, const void *d_
     rc = crthip_seq_decode(c, p, n, d_out, ostride, d_state);
     if (rc) return rc;
     return crthip_seq_weave(c, p, n, d_out, ostride, d_out_init, 0);
+}
+
+/* scratch of crthip_sequence_sets (the same lazily grown block as seq_scratch): set_first[n_sets + 1], tab[n] (first field of my
+ * set, my set), inc[n_sets] (incoming hsync, vsync, rn), then guess / changed / owner / latest for n fields */
+static int sets_scratch(crthip_ctx *c, int n_sets, int n, int outh, SetsScratch *sc)
+{
+    const auto up = [](size_t v) { return (v + 255) & ~(size_t) 255; };
+    const size_t o_tab = up(sizeof(int) * ((size_t) n_sets + 1)), o_inc = o_tab + up(sizeof(int2) * (size_t) n);
+    const size_t o_guess = o_inc + up(sizeof(int4) * (size_t) n_sets), o_changed = o_guess + up(sizeof(int2) * (size_t) n);
+    const size_t o_owner = o_changed + 256, o_latest = o_owner + up((size_t) n * outh);
+    const size_t need = o_latest + up(sizeof(int) * (size_t) n * outh);
+    if (need > c->seq_cap) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (c->d_seq) hipFree(c->d_seq);
+        c->d_seq = 0; c->seq_cap = 0;
+        if (hipMalloc((void **) &c->d_seq, need) != hipSuccess) return set_err(c, CRTHIP_E_NOMEM, "hipMalloc sequence scratch", hipSuccess);
+        c->seq_cap = need;
+    }
+    c->seq_guess_n = 0;                                 /* whatever crthip_seq_sync left in this block is gone */
+    sc->set_first = (int *) c->d_seq;
+    sc->tab = (int2 *) (c->d_seq + o_tab);
+    sc->inc = (int4 *) (c->d_seq + o_inc);
+    sc->guess = (int2 *) (c->d_seq + o_guess);
+    sc->changed = (int *) (c->d_seq + o_changed);
+    sc->owner = c->d_seq + o_owner;
+    sc->latest = (int *) (c->d_seq + o_latest);
+    return CRTHIP_OK;
+}
+
+int crthip_sequence_sets(crthip_ctx *c, const crthip_params *p, int n_sets, const int *set_first,
+                         const void *d_images, size_t istride, void *d_out, size_t ostride,
+                         const void *d_out_init, size_t out_init_stride, crthip_state *d_state, int *passes_out)
+{
+    if (!c || !p) return CRTHIP_E_ARG;
+    if (n_sets <= 0 || !set_first) return set_err(c, CRTHIP_E_ARG, "crthip_sequence_sets: no sets", hipSuccess);
+    if (set_first[0] != 0) return set_err(c, CRTHIP_E_ARG, "crthip_sequence_sets: set_first[0] must be 0", hipSuccess);
+    int max_len = 0;
+    for (int s = 0; s < n_sets; s++) {
+        if (set_first[s + 1] <= set_first[s])
+            return set_err(c, CRTHIP_E_ARG, "crthip_sequence_sets: set_first must be strictly ascending (every set has at least one field)", hipSuccess);
+        if (set_first[s + 1] - set_first[s] > max_len) max_len = set_first[s + 1] - set_first[s];
+    }
+    const int n = set_first[n_sets];
+    int rc = check_params(c, p, n);
+    if (rc) return rc;
+    if (!d_images || !d_out || !d_state) return CRTHIP_E_ARG;
+    if (p->out_bpp == 0) return CRTHIP_OK;                /* as crthip_sequence */
+    if (c->system == CRTHIP_SYSTEM_NTSCVHS && !(p->flags & CRTHIP_F_VHS_LCG_NOISE))
+        return set_err(c, CRTHIP_E_ARG, "crthip_sequence_sets: the VHS build with rand() noise is not available (every set would own a rand() stream); "
+                                        "use CRTHIP_F_VHS_LCG_NOISE or crthip_sequence per set", hipSuccess);
+    if (c->system == CRTHIP_SYSTEM_NTSCVHS && (p->flags & CRTHIP_F_VHS_DRAW_ABERRATION))
+        return set_err(c, CRTHIP_E_ARG, "crthip_sequence_sets: CRTHIP_F_VHS_DRAW_ABERRATION draws from the rand() stream; give the heights in d_state[k].aux", hipSuccess);
+    rc = seq_check(c, p, n);
+    if (rc) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (n > c->cap_fields) {
+        rc = crthip_reserve(c, n);
+        if (rc) return rc;
+    }
+    SetsScratch sc;
+    rc = sets_scratch(c, n_sets, n, p->outh, &sc);
+    if (rc) return rc;
+    /* the set table: built here, uploaded once (the host copy belongs to the context: it outlives the copy) */
+    const size_t tab_ints = (size_t) n_sets + 1, host_ints = ((tab_ints + 63) & ~(size_t) 63) + 2 * (size_t) n;
+    if (host_ints > c->seq_sets_host_cap) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        free(c->seq_sets_host);
+        c->seq_sets_host_cap = 0;
+        c->seq_sets_host = (int *) malloc(sizeof(int) * host_ints);
+        if (!c->seq_sets_host) return set_err(c, CRTHIP_E_NOMEM, "crthip_sequence_sets: set table", hipSuccess);
+        c->seq_sets_host_cap = host_ints;
+    }
+    int *h_first = c->seq_sets_host, *h_tab = c->seq_sets_host + ((tab_ints + 63) & ~(size_t) 63);
+    for (int s = 0; s <= n_sets; s++) h_first[s] = set_first[s];
+    for (int s = 0; s < n_sets; s++)
+        for (int k = set_first[s]; k < set_first[s + 1]; k++) { h_tab[2 * k] = set_first[s]; h_tab[2 * k + 1] = s; }
+    HIPCHK(c, hipMemcpyAsync(sc.set_first, h_first, sizeof(int) * tab_ints, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(sc.tab, h_tab, sizeof(int2) * (size_t) n, hipMemcpyHostToDevice, c->stream));
+    /* as crthip_seq_encode: the flat signal layout, the encoder's tables */
+    c->last_lay.pitch = c->sd.hres; c->last_lay.shift = 0; c->last_lay.padv = 0; c->last_lay.wrap = 0; c->last_lay.fstride = c->fstride;
+    c->last_n = n;
+    rc = crt_run_encoder_prepare(c, p, true);
+    if (rc) return rc;
+    const dim3 gn((n + 63) / 64), gs((n_sets + 63) / 64), b64(64);
+    hipLaunchKernelGGL(k_sets_incoming, gs, b64, 0, c->stream, n_sets, sc.set_first, d_state, sc.inc);
+    hipLaunchKernelGGL(k_sets_rn, gn, b64, 0, c->stream, n, d_state, sc.tab, sc.inc, sc.guess, c->whole_field);
+    rc = crt_run_encoder(c, p, n, d_images, istride, c->d_inp, d_state, true, 1, false);
+    if (rc) return rc;
+    /* the joint fixed point: one flag for all sets; after pass j the first j fields of every set are final */
+    int passes = 0;
+    const crthip_params q = with_signal_envelope(p);
+    for (;;) {
+        passes++;
+        HIPCHK(c, hipMemsetAsync(sc.changed, 0, sizeof(int), c->stream));
+        hipLaunchKernelGGL(k_sets_load, gn, b64, 0, c->stream, n, d_state, sc.tab, sc.inc, sc.guess);
+        rc = crt_run_encoder_state(c, p, n, d_state);
+        if (rc) return rc;
+        rc = crt_run_sync(c, &q, n, c->d_inp, d_state, c->d_lines, 0);
+        if (rc) return rc;
+        hipLaunchKernelGGL(k_seq_compare, gn, b64, 0, c->stream, n, d_state, sc.guess, sc.changed);
+        int flag = 0;
+        HIPCHK(c, hipMemcpyAsync(&flag, sc.changed, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (!flag) break;
+        if (passes > max_len + 1)
+            return set_err(c, CRTHIP_E_HIP, "crthip_sequence_sets: the sync chain over the fields did not converge", hipSuccess);
+    }
+    if (passes_out) *passes_out = passes;
+    crt_run_advance_rn(c, n, d_state);
+    crthip_params pb = *p;
+    pb.blend = 0;
+    rc = crt_run_decode(c, &pb, n, c->d_inp, c->d_lines, d_out, ostride);
+    if (rc) return rc;
+    const int outh = p->outh;
+    if (p->blend) {
+        HIPCHK(c, hipMemsetAsync(sc.latest, 0xff, sizeof(int) * (size_t) n * outh, c->stream));       /* -1 everywhere */
+        hipLaunchKernelGGL(k_seq_rowsrc, dim3((n * c->sd.lines + 255) / 256), dim3(256), 0, c->stream, n, c->sd.lines, outh, c->d_lines, sc.latest);
+    } else {
+        HIPCHK(c, hipMemsetAsync(sc.owner, 0, (size_t) n * outh, c->stream));
+        hipLaunchKernelGGL(k_seq_rows, dim3((n * c->sd.lines + 255) / 256), dim3(256), 0, c->stream, n, c->sd.lines, outh, c->d_lines, sc.owner);
+        hipLaunchKernelGGL(k_sets_latest, dim3((n_sets * outh + 63) / 64), dim3(64), 0, c->stream, n_sets, outh, sc.set_first, sc.owner, sc.latest);
+    }
+    const int ph = phosphor_mode(p);
+    unsigned char *out = (unsigned char *) d_out;
+    const unsigned char *init = (const unsigned char *) d_out_init;
+    if (ph == PH_FADE) launch_sets_weave<PH_FADE>(c, p, n_sets, n, max_len, out, ostride, init, out_init_stride, sc);
+    else if (ph == PH_CLEAR) launch_sets_weave<PH_CLEAR>(c, p, n_sets, n, max_len, out, ostride, init, out_init_stride, sc);
+    else launch_sets_weave<PH_KEEP>(c, p, n_sets, n, max_len, out, ostride, init, out_init_stride, sc);
+    HIPCHK(c, hipGetLastError());
+    return CRTHIP_OK;
 }
 
 int crthip_set_shape(crthip_ctx *c, int shape)
