@@ -187,7 +187,7 @@ template <class S> struct PadGeom {
     static constexpr int DECWIN = (((S::AV_LEN + 3) / 4 + 15) / 16) * 64;   /* bytes every decoder shape reads from crthip_line.pos at most */
     static constexpr int SCR_LINE0 = S::VRES + 1;                      /* first scratch row (one per decoded line) */
     static constexpr size_t FSTRIDE = (size_t) (S::VRES + 1 + S::LINES) * PITCH;
-    static_assert(DECWIN + 16 <= PITCH && PADW >= 96, "a decoder window fits a scratch row; the pad holds the sync windows");
+    static_assert(DECWIN + 128 <= PITCH && PADW >= 96, "a decoder window fits a scratch row behind any shift (0..127); the pad holds the sync windows");
 };
 /* what the host decides per field-pass (crt_fused_layout, crt_host.hip) */
 struct sig_layout {

@@ -982,8 +982,9 @@ int crthip_fieldpass(crthip_ctx *c, const crthip_params *p, int n, const void *d
     if (enc != 0 || vhs_rand_path || !crt_fused_layout(c, p, n, &lay)) {
         lay.pitch = c->sd.hres; lay.shift = 0; lay.padv = 0; lay.wrap = 0; lay.fstride = c->fstride;
     }
-    c->last_lay = lay;
-    c->last_n = n;
+    /* what crthip_fieldpass_signal may unpad is the signal of the last pass that was enqueued COMPLETELY: a pass refused half-way
+     * (the decoder's argument checks come after the encoder and the sync chain) leaves no claim on the workspace */
+    c->last_n = 0;
     /* 0 = automatic.  The idea: run the vector / latency bound encoder + sync chain of one chunk under the HBM-write
      * bound decoder of the previous one.  Measured on MI355X (profiles/r02_overlap_sweep.txt): at 1080p the encoder's
      * image reads and the decoder's picture writes already saturate what HBM delivers for this access mix, running
@@ -1025,6 +1026,8 @@ int crthip_fieldpass(crthip_ctx *c, const crthip_params *p, int n, const void *d
     }
     if (rc) return rc;
     HIPCHK(c, hipGetLastError());
+    c->last_lay = lay;
+    c->last_n = n;
     return CRTHIP_OK;
 }
 
@@ -1133,9 +1136,7 @@ int crthip_seq_encode(crthip_ctx *c, const crthip_params *p, int n, int first_in
         if (rc) return rc;
     }
     c->seq_guess_n = 0;                                    /* a new video: no warm start for the sync chain */
-    /* sequence mode keeps the reference's flat signal layout (its phases are separate calls over the same workspace) */
-    c->last_lay.pitch = c->sd.hres; c->last_lay.shift = 0; c->last_lay.padv = 0; c->last_lay.wrap = 0; c->last_lay.fstride = c->fstride;
-    c->last_n = n;
+    c->last_n = 0;                                         /* (recorded below, once the signal is enqueued) */
     rc = crt_run_encoder_prepare(c, p, true);
     if (rc) return rc;
     if (vhs) {
@@ -1160,6 +1161,9 @@ int crthip_seq_encode(crthip_ctx *c, const crthip_params *p, int n, int first_in
         if (rc) return rc;
     }
     HIPCHK(c, hipGetLastError());
+    /* sequence mode keeps the reference's flat signal layout (its phases are separate calls over the same workspace) */
+    c->last_lay.pitch = c->sd.hres; c->last_lay.shift = 0; c->last_lay.padv = 0; c->last_lay.wrap = 0; c->last_lay.fstride = c->fstride;
+    c->last_n = n;
     return CRTHIP_OK;
 }
 
@@ -1403,9 +1407,8 @@ int crthip_sequence_sets(crthip_ctx *c, const crthip_params *p, int n_sets, cons
         for (int k = set_first[s]; k < set_first[s + 1]; k++) { h_tab[2 * k] = set_first[s]; h_tab[2 * k + 1] = s; }
     HIPCHK(c, hipMemcpyAsync(sc.set_first, h_first, sizeof(int) * tab_ints, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(sc.tab, h_tab, sizeof(int2) * (size_t) n, hipMemcpyHostToDevice, c->stream));
-    /* as crthip_seq_encode: the flat signal layout, the encoder's tables */
-    c->last_lay.pitch = c->sd.hres; c->last_lay.shift = 0; c->last_lay.padv = 0; c->last_lay.wrap = 0; c->last_lay.fstride = c->fstride;
-    c->last_n = n;
+    /* as crthip_seq_encode: the encoder's tables, and the flat signal layout (recorded once the whole call is enqueued) */
+    c->last_n = 0;
     rc = crt_run_encoder_prepare(c, p, true);
     if (rc) return rc;
     const dim3 gn((n + 63) / 64), gs((n_sets + 63) / 64), b64(64);
@@ -1454,6 +1457,8 @@ int crthip_sequence_sets(crthip_ctx *c, const crthip_params *p, int n_sets, cons
     else if (ph == PH_CLEAR) launch_sets_weave<PH_CLEAR>(c, p, n_sets, n, max_len, out, ostride, init, out_init_stride, sc);
     else launch_sets_weave<PH_KEEP>(c, p, n_sets, n, max_len, out, ostride, init, out_init_stride, sc);
     HIPCHK(c, hipGetLastError());
+    c->last_lay.pitch = c->sd.hres; c->last_lay.shift = 0; c->last_lay.padv = 0; c->last_lay.wrap = 0; c->last_lay.fstride = c->fstride;
+    c->last_n = n;
     return CRTHIP_OK;
 }
 
