@@ -315,6 +315,51 @@ int  crthip_sequence_sets(crthip_ctx *ctx, const crthip_params *p,
                           crthip_state *d_state, int *passes);
 
 /*
+ * STILLS: finished still pictures for a batch of n images -- what the reference's main program does for one image
+ * (`ntsc -op 640 480 0 0 in.ppm out.ppm`; the accumulate loop of crt_main.c:241-255 with blend = 1, scanlines = 1): several
+ * field-passes over the SAME image onto the SAME output buffer, 4 when progressive, 8 when interlaced.
+ *
+ * crthip_stills_schedule (host only) writes that loop's passes: field = first_field & 1, frame = 0; for e = 0 .. n_frames - 1:
+ * emit (field, frame); if interlaced: toggle field, emit again, toggle frame when e is even (the field is not reset between
+ * iterations, as in the CLI); aux = 0.  Interlaced from field 0: (0,0)(1,0)(1,1)(0,1)(0,1)(1,1)(1,0)(0,0) -- four distinct entries,
+ * each used twice; progressive: one entry n_frames times.  Returns the number of passes written (n_frames, or 2 * n_frames), or
+ * CRTHIP_E_ARG (sched == NULL, n_frames <= 0, more passes than `cap` or than CRTHIP_STILLS_MAX_PASSES).
+ *
+ * crthip_stills: bit for bit and state for state what n_passes calls of crthip_fieldpass give on the same n images, the same d_out
+ * and the same d_state, with d_state[k].field / .frame / .aux = sched[r] (field and frame masked with 1, crt_ntsc.c:197-198; aux =
+ * dot_crawl_offset or the VHS aberration height, as in crthip_state) set on the device before call r:
+ *   d_out image k = still k's display before pass 0 (zeros for the CLI), the finished still on return;
+ *   d_state[k]    = hsync / vsync / rn / ccf in; on return the state after the last pass, with the last pass's field / frame / aux
+ *                   (rand()-noise VHS build: the bound histories carry every still's generator the same way);
+ *   everything crthip_fieldpass accepts is accepted with the same meaning, per pass (every system, bloom, FIR, formats, kernel
+ *   shapes, both signal layouts, CRTHIP_F_NES_SETUP, the phosphor flags: one display step per pass); what it refuses is refused,
+ *   and so are n_passes <= 0, n_passes > CRTHIP_STILLS_MAX_PASSES and sched == NULL (CRTHIP_E_ARG, crthip_error_string says why).
+ *   A refused call leaves d_out and d_state untouched.
+ * What the call adds over the loop:
+ *   - noise == 0 (the CLI's test configuration) on the fused LCG-noise path (not the rand()-noise VHS build, not CRTHIP_F_NO_VSYNC,
+ *     not an input format crt_modulate refuses): crt_modulate writes the same samples whatever the pass, so the clean signal of
+ *     every DISTINCT (field, frame, aux) of the schedule is encoded ONCE for the batch -- 4 encoder runs instead of 8 for the
+ *     interlaced CLI schedule, 1 instead of 4 for the progressive one -- into a workspace of n_distinct x n fields (in the layout a
+ *     field-pass of n fields would take), which the sync chain and the decoder of every pass read; rn, the ccf preset and the VHS
+ *     hsync reset are still applied per pass.  Any other noise encodes per pass, as the loop does.
+ *   - one asynchronous call: after crthip_stills_reserve(ctx, n, n_distinct) it allocates nothing and does not synchronise with the
+ *     host (the schedule entries travel as kernel arguments), so it can be captured into a HIP graph like crthip_fieldpass.
+ *     Without the reserve the workspace grows on demand.
+ *   - the shared signal lives in a workspace of its own: nothing of it is seen by a following crthip_fieldpass / crthip_sequence*
+ *     on the same context, nor the other way round.  crthip_fieldpass_signal after crthip_stills is refused (the passes of a still
+ *     may have read different signals; there is no "the" signal of the call).
+ */
+typedef struct crthip_pass { int field, frame, aux, reserved; } crthip_pass;     /* 16 bytes */
+#define CRTHIP_STILLS_MAX_PASSES 64
+int  crthip_stills_schedule(int interlaced, int first_field, int n_frames, crthip_pass *sched, int cap);
+/* workspace for stills of up to n images whose schedules have up to n_distinct distinct entries (plus crthip_reserve(ctx, n)) */
+int  crthip_stills_reserve(crthip_ctx *ctx, int n, int n_distinct);
+int  crthip_stills(crthip_ctx *ctx, const crthip_params *p, int n,
+                   const void *d_images, size_t image_stride,
+                   void *d_out, size_t out_stride, crthip_state *d_state,
+                   int n_passes, const crthip_pass *sched /* host */);
+
+/*
  * The phases of crthip_sequence, for hosts that cut ONE video over several contexts / devices / processes
  * (include/crt_hip_node.h; ntsc-crt_amd/shard.py over torch.distributed).  A shard holds the n consecutive fields
  * [first_index, first_index + n) of the video; crthip_sequence == encode(0, rn0) + sync + decode + weave on one context.
@@ -408,7 +453,8 @@ int  crthip_set_signal_tile(crthip_ctx *ctx, int dwords);
  * of new contexts.
  * crthip_fieldpass_signal: the noisy signal of the first n fields of the context's LAST crthip_fieldpass, repacked into the
  * reference's layout (n fields at crthip_field_stride() spacing: CRT_INPUT_SIZE samples + the CRTHIP_TAIL mirror), i.e. what
- * crt_demodulate leaves in CRT.inp -- for parity tests of the fused path; *padded (optional) tells which layout it came from. */
+ * crt_demodulate leaves in CRT.inp -- for parity tests of the fused path; *padded (optional) tells which layout it came from.
+ * Refused after crthip_stills (see there). */
 int  crthip_set_signal_layout(crthip_ctx *ctx, int padded);
 /* Host only (no device needed): which layout a crthip_fieldpass of n_fields with these (finalized) parameters takes under the default
  * switches and kernel shape `shape` (crthip_set_shape) -- returns 1 = padded, 0 = flat, < 0 = error; layout[] = { bytes between line

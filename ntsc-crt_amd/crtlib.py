@@ -57,6 +57,14 @@ def variant_flags(name):
     return VARIANTS[name][1] if name in VARIANTS else 0
 
 
+class Pass(C.Structure):
+    """crthip_pass (include/crt_hip.h): the encoder inputs of one pass of a stills schedule."""
+    _fields_ = [("field", C.c_int), ("frame", C.c_int), ("aux", C.c_int), ("reserved", C.c_int)]
+
+
+STILLS_MAX_PASSES = 64
+
+
 class Params(C.Structure):
     """crthip_params (include/crt_hip.h)."""
     _fields_ = [(n, C.c_int) for n in (
@@ -133,6 +141,9 @@ def load_library():
     L.crthip_table_generation.restype = C.c_uint
     L.crthip_sequence.argtypes = [vp, PP, ci, vp, sz, vp, sz, vp, vp, C.POINTER(ci)]
     L.crthip_sequence_sets.argtypes = [vp, PP, ci, C.POINTER(ci), vp, sz, vp, sz, vp, sz, vp, C.POINTER(ci)]
+    L.crthip_stills_schedule.argtypes = [ci, ci, ci, C.POINTER(Pass), ci]
+    L.crthip_stills_reserve.argtypes = [vp, ci, ci]
+    L.crthip_stills.argtypes = [vp, PP, ci, vp, sz, vp, sz, vp, ci, C.POINTER(Pass)]
     L.crthip_vhs_chain.argtypes = [vp, ci, vp, ci]
     L.crthip_seq_vhs_prechained.argtypes = [vp, ci]
     L.crthip_seq_encode.argtypes = [vp, PP, ci, ci, ci, vp, sz, vp]
@@ -176,6 +187,16 @@ def phosphor_table(age):
     if rc:
         raise ValueError("crthip_phosphor_table failed (%d)" % rc)
     return bytes(lut)
+
+
+def stills_schedule(interlaced=True, first_field=0, frames=4):
+    """crthip_stills_schedule (host only): the passes of the reference's `ntsc` program (crt_main.c:241-255) as a list of
+    (field, frame, aux) -- `frames` passes when progressive, 2 * frames when interlaced; frames = 4 is the CLI."""
+    buf = (Pass * STILLS_MAX_PASSES)()
+    n = load_library().crthip_stills_schedule(int(bool(interlaced)), int(first_field), int(frames), buf, STILLS_MAX_PASSES)
+    if n < 0:
+        raise ValueError("crthip_stills_schedule failed (%d)" % n)
+    return [(buf[r].field, buf[r].frame, buf[r].aux) for r in range(n)]
 
 
 class Settings:
@@ -385,6 +406,30 @@ class CRT:
                                      self._image_stride(s), C.c_void_p(self.out.data_ptr()),
                                      self.out.stride(0), C.c_void_p(self.state.data_ptr()))
         self._check(rc, "crthip_fieldpass")
+        s.initialized = 1
+
+    def stills_reserve(self, n_distinct):
+        """Size the workspace of stills() for schedules of up to n_distinct distinct (field, frame, aux) entries: the call then
+        allocates nothing (a timed region, a HIP graph)."""
+        self._check(self.L.crthip_stills_reserve(self.ctx, self.n, int(n_distinct)), "crthip_stills_reserve")
+
+    def stills(self, s, noise, interlaced=True, first_field=0, frames=4, schedule=None):
+        """Finished stills of the n images of ``s``: the passes of the reference's `ntsc` program (crt_main.c:241-255; set
+        ``blend = scanlines = 1`` for its pictures) on ``self.out`` / ``self.state`` as they stand -- a fresh CRT is crt_init:
+        zeros, rn 194.  ``schedule``: a list of (field, frame) or (field, frame, aux) per pass instead of the CLI's, e.g. dot-crawl
+        offsets r % CRT_CC_VPER in aux for NES / PV-1000, aberration heights for VHS.  At noise 0 every distinct entry is encoded
+        once.  ``s.field`` / ``s.frame`` / ``s.dot_crawl_offset`` / ``s.aberration`` are not used: the schedule gives them."""
+        sched = stills_schedule(interlaced, first_field, frames) if schedule is None else [tuple(e) for e in schedule]
+        if not 0 < len(sched) <= STILLS_MAX_PASSES:
+            raise ValueError("a stills schedule has 1 .. %d passes, not %d" % (STILLS_MAX_PASSES, len(sched)))
+        buf = (Pass * len(sched))()
+        for r, e in enumerate(sched):
+            buf[r].field, buf[r].frame, buf[r].aux = int(e[0]), int(e[1]), int(e[2]) if len(e) > 2 else 0
+        p = self.params(s, noise)
+        rc = self.L.crthip_stills(self.ctx, C.byref(p), self.n, C.c_void_p(s.data.data_ptr()), self._image_stride(s),
+                                  C.c_void_p(self.out.data_ptr()), self.out.stride(0), C.c_void_p(self.state.data_ptr()),
+                                  len(sched), buf)
+        self._check(rc, "crthip_stills")
         s.initialized = 1
 
     def sequence(self, s, noise, out_init=None):

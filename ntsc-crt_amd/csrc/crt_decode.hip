@@ -34,12 +34,10 @@ static int decoder_min_tier(const crthip_ctx *c, const crthip_params *p)
     return c->no_loskip ? 2 : 0;                /* crthip_set_exact(3): keep the I/Q low cascades = the 24-bit tier */
 }
 
-int crt_run_decode(crthip_ctx *c, const crthip_params *p, int n, const signed char *d_inp,
-                   const crthip_line *d_lines, void *d_out, size_t ostride, size_t fstride)
+/* what the decoder refuses, whatever the fields hold: checked by crt_run_decode before it launches anything, and by crthip_stills
+ * before its first pass (a refused call must not have run the passes in front of its first decoder) */
+int crt_decode_check(crthip_ctx *c, const crthip_params *p)
 {
-    /* fstride: bytes between the fields of d_inp -- the flat layout's (0) or the padded one's of the fused path (crt_dev.h, sig_layout);
-     * crthip_line.pos is an offset into the field either way, the kernels do not know the difference */
-    if (!fstride) fstride = c->fstride;
     if (p->dx <= 0)     /* more than 4096 output pixels per sample: the resampler's step (crt_core.c:528) rounds to 0 */
         return set_err(c, CRTHIP_E_ARG, "outw too large for the 12-bit resampler (dx == 0)", hipSuccess);
     /* kernel shape (crthip_set_shape): the FIR build only exists in the lane-per-scanline shape; a bloom build has a
@@ -55,6 +53,19 @@ int crt_run_decode(crthip_ctx *c, const crthip_params *p, int n, const signed ch
             for (int b = 0; b < 3; b++)
                 if (p->eq_g[k][b] != want[k][b])
                     return set_err(c, CRTHIP_E_ARG, "equaliser gains differ from crt_core.c:272-286", hipSuccess);
+    }
+    return CRTHIP_OK;
+}
+
+int crt_run_decode(crthip_ctx *c, const crthip_params *p, int n, const signed char *d_inp,
+                   const crthip_line *d_lines, void *d_out, size_t ostride, size_t fstride)
+{
+    /* fstride: bytes between the fields of d_inp -- the flat layout's (0) or the padded one's of the fused path (crt_dev.h, sig_layout);
+     * crthip_line.pos is an offset into the field either way, the kernels do not know the difference */
+    if (!fstride) fstride = c->fstride;
+    {
+        const int rc = crt_decode_check(c, p);
+        if (rc) return rc;
     }
     /* ... and a WIDE picture leaves the scanline-parallel shape early: from WIDE_SHAPE_MIN_FIELDS fields on the wide-run decoder
      * (crt_decode4.hip: 16 scanlines per wave, so 32 fields are already two waves per CU) is the faster one -- 1080p x 64: 0.178 ->

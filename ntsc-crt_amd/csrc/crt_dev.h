@@ -558,6 +558,12 @@ struct crthip_ctx {
     size_t fstride_pad;         /* PadGeom::FSTRIDE of the context's system: d_inp is sized for it */
     sig_layout last_lay;        /* the layout of d_inp's current contents (crthip_fieldpass_signal) */
     int last_n;
+    /* crthip_stills: the clean signal of every distinct schedule entry, n_distinct x n fields (a workspace of its own: nothing else
+     * reads or writes it), its size in bytes, and the layout (pitch, shift, field stride) of what it holds -- the bytes every layout
+     * takes for zero without writing them are cleared when the layout changes */
+    signed char *d_still_sig;
+    size_t still_cap;
+    sig_layout still_lay;
     int wide_order_env, dec_order_env, act_order_env;   /* CRTHIP_WIDE_ORDER / _DEC_ORDER / _ACT_ORDER: workgroup order of k_decode_wide / k_decode / k_active
                                                            (block_item above): 0 = the default, K > 1 = that many strides, -1 = one stride per field, 1 = in order */
     int sig_tile_env;           /* CRTHIP_SIG_TILE = 16 | 32 | 64: pins k_active's small / large signal tile (A/B measurements); 0 = by batch size */
@@ -689,6 +695,7 @@ int crt_run_sync(crthip_ctx *c, const crthip_params *p, int n, const signed char
                  crthip_line *d_lines, int advance_rn, int preset_ccf = 0, const sig_layout *lay = nullptr);
 int crt_run_decode(crthip_ctx *c, const crthip_params *p, int n, const signed char *d_inp,
                    const crthip_line *d_lines, void *d_out, size_t ostride, size_t fstride = 0);   /* fstride 0: the flat layout's */
+int crt_decode_check(crthip_ctx *c, const crthip_params *p);
 bool crt_decode_wide_ok(const crthip_ctx *c, const crthip_params *p, int min_tier, bool wide);
 int crt_run_decode_wide(crthip_ctx *c, const crthip_params *p, int n, const signed char *d_inp, const crthip_line *d_lines,
                         void *d_out, size_t ostride, int min_tier, int rank, size_t fstride);

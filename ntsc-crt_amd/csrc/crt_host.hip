@@ -432,6 +432,21 @@ k_sets_blend_step(int j, int outh, size_t pitch, unsigned char *out, size_t ostr
 }
 
 
+/* ------------------------------------------------------------------------- */
+/* Stills (crthip_stills): several field-passes of the same images onto the same pictures */
+/* ------------------------------------------------------------------------- */
+/* the encoder inputs of one pass of the schedule into every still's state, before the pass (field and frame masked as
+ * crt_ntsc.c:197-198 does); `pass` arrives as a kernel argument: nothing of the schedule lives in memory */
+__global__ void k_stills_pass(int n, crthip_state *state, crthip_pass pass)
+{
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    state[k].field = pass.field & 1;
+    state[k].frame = pass.frame & 1;
+    state[k].aux = pass.aux;
+}
+
+
 /* (r6) the fused path's padded signal (crt_dev.h, sig_layout) back in the reference's flat layout, 16 samples per lane: what
  * crthip_fieldpass_signal hands out (tests compare it with the oracle's inp[] byte for byte; nothing in a field-pass needs it) */
 template <class S>
@@ -710,6 +725,7 @@ void crthip_destroy(crthip_ctx *c)
     if (c->d_vhs_dig) hipFree(c->d_vhs_dig);
     if (c->d_vhs_next) hipFree(c->d_vhs_next);
     if (c->d_seq) hipFree(c->d_seq);
+    if (c->d_still_sig) hipFree(c->d_still_sig);
     free(c->seq_sets_host);
     if (c->d_bloom) hipFree(c->d_bloom);
     if (c->table_stream) { hipStreamSynchronize(c->table_stream); hipStreamDestroy(c->table_stream); }
@@ -1028,6 +1044,140 @@ int crthip_fieldpass(crthip_ctx *c, const crthip_params *p, int n, const void *d
     HIPCHK(c, hipGetLastError());
     c->last_lay = lay;
     c->last_n = n;
+    return CRTHIP_OK;
+}
+
+/* ---- stills ---------------------------------------------------------------------------------------------------------------- */
+int crthip_stills_schedule(int interlaced, int first_field, int n_frames, crthip_pass *sched, int cap)
+{
+    if (!sched || n_frames <= 0 || n_frames > CRTHIP_STILLS_MAX_PASSES) return CRTHIP_E_ARG;
+    const int total = interlaced ? 2 * n_frames : n_frames;
+    if (total > cap || total > CRTHIP_STILLS_MAX_PASSES) return CRTHIP_E_ARG;
+    int field = first_field & 1, frame = 0, r = 0;
+    for (int e = 0; e < n_frames; e++) {                  /* crt_main.c:241-255 */
+        sched[r].field = field; sched[r].frame = frame; sched[r].aux = 0; sched[r].reserved = 0; r++;
+        if (interlaced) {
+            field ^= 1;
+            sched[r].field = field; sched[r].frame = frame; sched[r].aux = 0; sched[r].reserved = 0; r++;
+            if ((e & 1) == 0) frame ^= 1;                 /* a frame is two fields */
+        }
+    }
+    return r;
+}
+
+/* the shared-signal workspace for n_fields fields of `fstride` bytes (0: the largest a layout of this system takes) */
+static int stills_workspace(crthip_ctx *c, size_t n_fields, size_t fstride)
+{
+    if (!fstride) fstride = c->fstride_pad > c->fstride ? c->fstride_pad : c->fstride;
+    const size_t need = fstride * n_fields + 4096;
+    if (need <= c->still_cap) return CRTHIP_OK;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (c->d_still_sig) hipFree(c->d_still_sig);
+    c->d_still_sig = 0; c->still_cap = 0;
+    if (hipMalloc((void **) &c->d_still_sig, need) != hipSuccess) return set_err(c, CRTHIP_E_NOMEM, "hipMalloc stills signal workspace", hipSuccess);
+    c->still_cap = need;
+    c->still_lay.pitch = 0;                               /* holds nothing yet: the first call clears what it will use */
+    return CRTHIP_OK;
+}
+
+int crthip_stills_reserve(crthip_ctx *c, int n, int n_distinct)
+{
+    if (!c || n <= 0 || n_distinct <= 0 || n_distinct > CRTHIP_STILLS_MAX_PASSES) return CRTHIP_E_ARG;
+    HIPCHK(c, hipSetDevice(c->device));
+    const int rc = crthip_reserve(c, n);
+    if (rc) return rc;
+    return stills_workspace(c, (size_t) n * n_distinct, 0);
+}
+
+int crthip_stills(crthip_ctx *c, const crthip_params *p, int n, const void *d_images, size_t istride,
+                  void *d_out, size_t ostride, crthip_state *d_state, int n_passes, const crthip_pass *sched)
+{
+    int rc = check_params(c, p, n);
+    if (rc) return rc;
+    if (n_passes <= 0 || n_passes > CRTHIP_STILLS_MAX_PASSES)
+        return set_err(c, CRTHIP_E_ARG, "crthip_stills: n_passes must be 1 .. CRTHIP_STILLS_MAX_PASSES", hipSuccess);
+    if (!sched) return set_err(c, CRTHIP_E_ARG, "crthip_stills: no schedule (sched == NULL)", hipSuccess);
+    if (!d_images || !d_out || !d_state) return set_err(c, CRTHIP_E_ARG, "crthip_stills: null device pointer", hipSuccess);
+    const bool vhs_rand = c->system == CRTHIP_SYSTEM_NTSCVHS && !(p->flags & CRTHIP_F_VHS_LCG_NOISE);
+    if (vhs_rand && !c->d_vhs_hist)
+        return set_err(c, CRTHIP_E_ARG, "VHS: no generator histories bound (crthip_vhs_bind_history)", hipSuccess);
+    const int enc = check_encoder(c, p);
+    if (enc < 0) return enc;
+    if (p->out_bpp != 0) {
+        /* what the decoder of pass 0 would refuse, before anything runs */
+        rc = crt_decode_check(c, p);
+        if (rc) return rc;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    if (n > c->cap_fields) {
+        rc = crthip_reserve(c, n);
+        if (rc) return rc;
+    }
+    if (enc == 0) {
+        rc = crt_run_encoder_prepare(c, p, true);
+        if (rc) return rc;
+    }
+    /* the layout a field-pass of these n fields takes (crthip_fieldpass) */
+    sig_layout lay;
+    if (enc != 0 || vhs_rand || !crt_fused_layout(c, p, n, &lay)) {
+        lay.pitch = c->sd.hres; lay.shift = 0; lay.padv = 0; lay.wrap = 0; lay.fstride = c->fstride;
+    }
+    c->last_n = 0;                                        /* crthip_fieldpass_signal: refused after a stills call (crt_hip.h) */
+    const dim3 gn((n + 63) / 64), b64(64);
+    const bool shared = p->noise == 0 && enc == 0 && !vhs_rand && !(p->flags & CRTHIP_F_NO_VSYNC) && p->out_bpp != 0;
+    if (!shared) {
+        /* the loop itself: every pass encodes (its noise differs from pass to pass), in the field-pass workspace */
+        for (int r = 0; r < n_passes; r++) {
+            hipLaunchKernelGGL(k_stills_pass, gn, b64, 0, c->stream, n, d_state, sched[r]);
+            rc = fieldpass_chunk(c, p, enc, 0, n, 7, lay, d_images, istride, d_out, ostride, d_state);
+            if (rc) return rc;
+        }
+        HIPCHK(c, hipGetLastError());
+        return CRTHIP_OK;
+    }
+    /* noise 0: the clean signal of every distinct entry once, slot[r] = where pass r's signal is */
+    int slot[CRTHIP_STILLS_MAX_PASSES], first_of[CRTHIP_STILLS_MAX_PASSES], n_distinct = 0;
+    for (int r = 0; r < n_passes; r++) {
+        int e = 0;
+        while (e < n_distinct && !((sched[first_of[e]].field & 1) == (sched[r].field & 1) && (sched[first_of[e]].frame & 1) == (sched[r].frame & 1) &&
+                                   sched[first_of[e]].aux == sched[r].aux)) e++;
+        if (e == n_distinct) first_of[n_distinct++] = r;
+        slot[r] = e;
+    }
+    rc = stills_workspace(c, (size_t) n * n_distinct, lay.fstride);
+    if (rc) return rc;
+    if (c->still_lay.pitch != lay.pitch || c->still_lay.shift != lay.shift || c->still_lay.fstride != lay.fstride) {
+        /* another layout than the one the workspace last held (or none yet): the bytes a layout reads without ever writing them --
+         * the slack behind a flat field, the pads beyond the copies, the line behind the tail -- are zero for every call */
+        HIPCHK(c, hipMemsetAsync(c->d_still_sig, 0, c->still_cap, c->stream));
+        c->still_lay = lay;
+    }
+    const size_t slot_bytes = lay.fstride * (size_t) n;
+    for (int e = 0; e < n_distinct; e++) {
+        hipLaunchKernelGGL(k_stills_pass, gn, b64, 0, c->stream, n, d_state, sched[first_of[e]]);
+        rc = crt_run_encoder(c, p, n, d_images, istride, c->d_still_sig + (size_t) e * slot_bytes, d_state, true, 1, false, &lay);
+        if (rc) return rc;
+    }
+    /* what crt_modulate leaves in the state is applied per pass: by the sync chain's own waves (preset_ccf), or -- VHS, which also
+     * resets hsync there -- by k_encoder_state, exactly as a field-pass does */
+    const bool preset = c->system != CRTHIP_SYSTEM_NTSCVHS;
+    const crthip_params q = with_signal_envelope(p);
+    unsigned char *out = (unsigned char *) d_out;
+    for (int r = 0; r < n_passes; r++) {
+        const signed char *sig = c->d_still_sig + (size_t) slot[r] * slot_bytes;
+        hipLaunchKernelGGL(k_stills_pass, gn, b64, 0, c->stream, n, d_state, sched[r]);
+        if (!preset) {
+            rc = crt_run_encoder_state(c, p, n, d_state);
+            if (rc) return rc;
+        }
+        rc = crt_run_sync(c, &q, n, sig, d_state, c->d_lines, 1, preset ? 1 : 0, &lay);
+        if (rc) return rc;
+        if (phosphor_mode(p) == PH_FADE) launch_phosphor_rows<PH_FADE>(c, p, n, c->d_lines, out, ostride);
+        else if (phosphor_mode(p) == PH_CLEAR) launch_phosphor_rows<PH_CLEAR>(c, p, n, c->d_lines, out, ostride);
+        rc = crt_run_decode(c, p, n, sig, c->d_lines, out, ostride, lay.fstride);
+        if (rc) return rc;
+    }
+    HIPCHK(c, hipGetLastError());
     return CRTHIP_OK;
 }
 
