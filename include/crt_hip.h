@@ -462,6 +462,38 @@ int  crthip_set_signal_layout(crthip_ctx *ctx, int padded);
  * = bytes between the fields of the workspace.  (What crthip_reserve sizes the workspace for, and what the CPU tests check the
  * geometry rules with.) */
 int  crthip_signal_layout_query(const crthip_params *p, int n_fields, int shape, int layout[4], size_t *field_stride);
+
+/* The float form of the decoder's one-pole filter stages (k_decode, tiers 0 / 1 of the 4-sample systems).  A stage
+ * x' = x + ((c * (u - x) + 2^15) >> 16) runs as v_sub_f32 + v_fma_f32 in round-toward-minus-infinity on floats that hold x + bias
+ * inside [2^23, 2^24) (ulp 1).  With ce = c (x-form, 0 < c < 2^15: the chroma cascades) or c - 65536 (u-form, 2^15 <= c < 1.5 * 2^16:
+ * the luma ones) = +-2^k * odd, a = +-2^(15 - k) and n = (odd - 1) / 2:   (ce * d + 32768) >> 16 == floor(ce * (d + a) / 65536) - n.
+ * The bias of every state of a cascade moves by `drift` per sample (n, u-form: n + a), neighbouring stages are `dstage` apart
+ * (n - a, u-form: n), the input carries the bias of stage 0 plus a.  *_bits are float bit patterns: 0x4B000000 + value - 2^23.
+ * Cascades: 0 = luma low, 1 = luma high, 2 = I high, 3 = Q high. */
+typedef struct crthip_fstage_cascade {
+    int c, form, ce, a, n;          /* coefficient; 0 = x-form, 1 = u-form; effective coefficient; see above */
+    int drift, dstage;              /* bias step per sample; bias difference between stage j + 1 and stage j */
+    int mul_bits;                   /* float ce / 65536 (exact) */
+    int x0_bits, in0_bits, out0_bits;   /* bias of stage 0 before the first sample; of the first input; of stage 3 after the first sample */
+    int in_max, state_max;          /* envelope: |input|, |any state| */
+    int lo, hi;                     /* smallest / largest value any biased input or state can take over the line (verdict: inside the binade) */
+} crthip_fstage_cascade;
+typedef struct crthip_fstages {
+    int ok;                         /* the verdict: ranges_ok and a system of 4 samples per chroma cycle (the 5-sample decoder keeps
+                                       its carriers in LDS and its 1 487-sample lines on the integer stages) */
+    int ranges_ok;                  /* the arithmetic alone: coefficient ranges and every value inside the binade */
+    int steps;                      /* samples per line the ranges were evaluated for */
+    crthip_fstage_cascade cas[4];
+} crthip_fstages;
+/* Host only: constants, starting biases and verdict for these (finalized) parameters and `steps` samples per line (0: the system's
+ * AV_LEN + 1).  Returns the verdict (1: every input and state provably stays inside [2^23, 2^24) at the envelope of tiers 0 / 1 --
+ * any signal byte, |carrier| <= 120000, this |bright| --, the coefficient ranges hold and the system has 4 samples per chroma cycle;
+ * 0: the integer stages run), < 0 = error.  The cascades' constants are filled in wherever their coefficient is in range. */
+int  crthip_float_stages_query(const crthip_params *p, int steps, crthip_fstages *out);
+/* 1 if the context's last decoder call (stage-level or inside a field-pass) launched the float-stage kernels, 0 if the integer
+ * ones: the switch CRTHIP_DEC_FLOAT=0 (read when the context is created), a verdict of no, a batch whose brightness / contrast put it
+ * above tier 1, or a kernel shape without them (the scanline-parallel and wide-run decoders). */
+int  crthip_float_stages_used(const crthip_ctx *ctx);
 int  crthip_fieldpass_signal(crthip_ctx *ctx, int n, signed char *d_inp_flat, int *padded);
 /* Wide-run decoder (wide pictures, crt_decode4.hip): scanlines per wavefront.  0 (default) = by batch size (8 below 96 fields of
  * 1920x1080, 16 from there on), 8 / 16 = always that instantiation.  Same pictures either way (tests pin each instantiation to the

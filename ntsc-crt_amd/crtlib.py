@@ -84,6 +84,26 @@ class Params(C.Structure):
         ("col_step_lo", C.c_uint), ("col_step_hi", C.c_uint), ("loskip_wave_max", C.c_int), ("nes_border_color", C.c_int), ("reserved", C.c_int * 2)]
 
 
+class FStageCascade(C.Structure):
+    """crthip_fstage_cascade (include/crt_hip.h)."""
+    _fields_ = [(n, C.c_int) for n in ("c", "form", "ce", "a", "n", "drift", "dstage", "mul_bits", "x0_bits", "in0_bits", "out0_bits",
+                                       "in_max", "state_max", "lo", "hi")]
+
+
+class FStages(C.Structure):
+    """crthip_fstages (include/crt_hip.h): what crthip_float_stages_query reports."""
+    _fields_ = [("ok", C.c_int), ("ranges_ok", C.c_int), ("steps", C.c_int), ("cas", FStageCascade * 4)]
+
+
+def float_stages(params, steps=0):
+    """crthip_float_stages_query (host only): (verdict, FStages) for a finalized Params"""
+    out = FStages()
+    rc = load_library().crthip_float_stages_query(C.byref(params), int(steps), C.byref(out))
+    if rc < 0:
+        raise ValueError("crthip_float_stages_query failed (%d)" % rc)
+    return rc, out
+
+
 def bpp4fmt(fmt):
     return 3 if fmt in (0, 1) else (4 if fmt in (2, 3, 4, 5) else 0)
 
@@ -136,6 +156,9 @@ def load_library():
     L.crthip_set_wide_lpw.argtypes = [vp, ci]
     L.crthip_set_signal_layout.argtypes = [vp, ci]
     L.crthip_signal_layout_query.argtypes = [PP, ci, ci, C.POINTER(ci), C.POINTER(sz)]
+    if hasattr(L, "crthip_float_stages_query"):          # (an older build under CRTHIP_LIBDIR has neither)
+        L.crthip_float_stages_query.argtypes = [PP, ci, C.POINTER(FStages)]
+        L.crthip_float_stages_used.argtypes = [vp]
     L.crthip_fieldpass_signal.argtypes = [vp, ci, vp, C.POINTER(ci)]
     L.crthip_table_generation.argtypes = [vp]
     L.crthip_table_generation.restype = C.c_uint
@@ -537,6 +560,10 @@ class CRT:
     def set_signal_tile(self, dwords):
         """fieldpass(): the encoder's signal tile -- 0 by batch size (default), 16 = 64-byte store pieces, 32 / 64 = the large ones"""
         self._check(self.L.crthip_set_signal_tile(self.ctx, int(dwords)), "crthip_set_signal_tile")
+
+    def float_stages_used(self):
+        """did the last decoder call launch the float-stage kernels (crthip_float_stages_used)"""
+        return int(load_library().crthip_float_stages_used(self.ctx))
 
     def set_signal_layout(self, padded):
         """fieldpass(): 1 (default) = the signal between encoder and decoder in padded, aligned lines; 0 = the reference's flat layout"""

@@ -34,6 +34,25 @@ static int decoder_min_tier(const crthip_ctx *c, const crthip_params *p)
     return c->no_loskip ? 2 : 0;                /* crthip_set_exact(3): keep the I/Q low cascades = the 24-bit tier */
 }
 
+/* Float filter stages for tier group 0 (crt_decode_lane.h, eq_stepf_yiq)?  Yes where the switch is on (CRTHIP_DEC_FLOAT, default),
+ * the system has 4 samples per chroma cycle (the PV-1000's 1 487-sample lines stay on the integer stages) and the host's proof holds
+ * for these coefficients, this brightness and the system's line length (crthip_float_stages_query, crt_setup.c); *fs = the kernel's
+ * constants then.  Any no: the integer stages, as before. */
+bool crt_decode_fstages(crthip_ctx *c, const crthip_params *p, int min_tier, FStageArgs *fs)
+{
+    memset(fs, 0, sizeof *fs);
+    c->last_fstage = 0;
+    if (!c->dec_float || min_tier > 1) return false;
+    crthip_fstages q;
+    if (crthip_float_stages_query(p, 0, &q) != 1) return false;
+    for (int k = 0; k < 4; k++) {
+        fs->mul[k] = q.cas[k].mul_bits; fs->x0[k] = q.cas[k].x0_bits; fs->dstage[k] = q.cas[k].dstage;
+        fs->in0[k] = q.cas[k].in0_bits; fs->out0[k] = q.cas[k].out0_bits; fs->drift[k] = q.cas[k].drift;
+    }
+    c->last_fstage = 1;
+    return true;
+}
+
 /* what the decoder refuses, whatever the fields hold: checked by crt_run_decode before it launches anything, and by crthip_stills
  * before its first pass (a refused call must not have run the passes in front of its first decoder) */
 int crt_decode_check(crthip_ctx *c, const crthip_params *p)
@@ -63,6 +82,7 @@ int crt_run_decode(crthip_ctx *c, const crthip_params *p, int n, const signed ch
     /* fstride: bytes between the fields of d_inp -- the flat layout's (0) or the padded one's of the fused path (crt_dev.h, sig_layout);
      * crthip_line.pos is an offset into the field either way, the kernels do not know the difference */
     if (!fstride) fstride = c->fstride;
+    c->last_fstage = 0;
     {
         const int rc = crt_decode_check(c, p);
         if (rc) return rc;
@@ -80,6 +100,9 @@ int crt_run_decode(crthip_ctx *c, const crthip_params *p, int n, const signed ch
     const int min_tier = p->eq_kernel ? (decoder_min_tier(c, p) == 3 ? 5 : 4) : decoder_min_tier(c, p);
     const bool wide = wide_px;
     const bool use_wide = crt_decode_wide_ok(c, p, min_tier, wide);
+    FStageArgs fsa;
+    const bool fstage = crt_decode_fstages(c, p, min_tier, &fsa) && !use_wide;     /* (the wide-run decoder keeps its integer stages) */
+    c->last_fstage = fstage;
     /* lines per output row when the picture is shorter than the raster: one pass per rank */
     const unsigned span = (unsigned) p->outh + p->v_fac;
     const int passes = span >= (unsigned) c->sd.lines ? 1 : (int) (((unsigned) c->sd.lines + span - 1) / (span ? span : 1));
@@ -94,8 +117,12 @@ int crt_run_decode(crthip_ctx *c, const crthip_params *p, int n, const signed ch
         for (int rank = 0; rank < passes; rank++) {
 #define CRTHIP_LAUNCH_DECODE(TG, B3) \
     do { if constexpr (S::CCS != 4 && TG == 2) break; /* no FIR build of the 5-sample system */ \
-         else if (wide) hipLaunchKernelGGL((k_decode<S, TG, B3, 32>), grid, block, 0, c->stream, *p, n, d_inp, fstride, d_lines, o, ostride, min_tier, rank, (const int *) nullptr, bo.K, bo.per); \
-         else hipLaunchKernelGGL((k_decode<S, TG, B3, 16>), grid, block, 0, c->stream, *p, n, d_inp, fstride, d_lines, o, ostride, min_tier, rank, (const int *) nullptr, bo.K, bo.per); } while (0)
+         if constexpr (S::CCS == 4 && TG == 0) { if (fstage) { /* float filter stages */ \
+             if (wide) hipLaunchKernelGGL((k_decode<S, TG, B3, 32, false, true>), grid, block, 0, c->stream, *p, n, d_inp, fstride, d_lines, o, ostride, min_tier, rank, (const int *) nullptr, bo.K, bo.per, fsa); \
+             else hipLaunchKernelGGL((k_decode<S, TG, B3, 16, false, true>), grid, block, 0, c->stream, *p, n, d_inp, fstride, d_lines, o, ostride, min_tier, rank, (const int *) nullptr, bo.K, bo.per, fsa); \
+             break; } } \
+         if (wide) hipLaunchKernelGGL((k_decode<S, TG, B3, 32>), grid, block, 0, c->stream, *p, n, d_inp, fstride, d_lines, o, ostride, min_tier, rank, (const int *) nullptr, bo.K, bo.per, fsa); \
+         else hipLaunchKernelGGL((k_decode<S, TG, B3, 16>), grid, block, 0, c->stream, *p, n, d_inp, fstride, d_lines, o, ostride, min_tier, rank, (const int *) nullptr, bo.K, bo.per, fsa); } while (0)
             /* wide pictures in tiers 0 / 1: the 16-scanlines-per-wave kernel with 1 KB row runs (crt_decode4.hip); the groups
              * of the higher tiers stay with k_decode below */
             if (use_wide) {

@@ -132,6 +132,8 @@ int crt_run_decode_bloom_lanes(crthip_ctx *c, const crthip_params *p, int n, con
     /* tier 1 (carriers << 7 beyond 24 bits) exists for the NES, which has no bloom build, and for the PV-1000, whose default
      * saturation sits there; the 4-sample systems send such lines to tier 2 */
     if (min_tier == 1 && c->sd.cc_samples != 5) min_tier = 2;
+    FStageArgs fsa;
+    const bool fstage = crt_decode_fstages(c, p, min_tier, &fsa);
     return dispatch_system(c->system, c->pattern, [&](auto tag) {
         using S = decltype(tag);
         if constexpr (S::NES_TIMING) {
@@ -151,8 +153,12 @@ int crt_run_decode_bloom_lanes(crthip_ctx *c, const crthip_params *p, int n, con
             unsigned char *o = (unsigned char *) d_out;
             for (int rank = 0; rank < passes; rank++) {
 #define CRTHIP_LAUNCH_BLOOM(TG, B3) \
-    do { if (wide) hipLaunchKernelGGL((k_decode<S, TG, B3, 32, true>), grid, block, 0, c->stream, *p, n, d_inp, fstride, d_lines, o, ostride, min_tier, rank, (const int *) perm, 0, 0); \
-         else hipLaunchKernelGGL((k_decode<S, TG, B3, 16, true>), grid, block, 0, c->stream, *p, n, d_inp, fstride, d_lines, o, ostride, min_tier, rank, (const int *) perm, 0, 0); } while (0)
+    do { if constexpr (S::CCS == 4 && TG == 0) { if (fstage) { /* float filter stages (crt_decode.hip, crt_decode_fstages) */ \
+             if (wide) hipLaunchKernelGGL((k_decode<S, TG, B3, 32, true, true>), grid, block, 0, c->stream, *p, n, d_inp, fstride, d_lines, o, ostride, min_tier, rank, (const int *) perm, 0, 0, fsa); \
+             else hipLaunchKernelGGL((k_decode<S, TG, B3, 16, true, true>), grid, block, 0, c->stream, *p, n, d_inp, fstride, d_lines, o, ostride, min_tier, rank, (const int *) perm, 0, 0, fsa); \
+             break; } } \
+         if (wide) hipLaunchKernelGGL((k_decode<S, TG, B3, 32, true>), grid, block, 0, c->stream, *p, n, d_inp, fstride, d_lines, o, ostride, min_tier, rank, (const int *) perm, 0, 0, fsa); \
+         else hipLaunchKernelGGL((k_decode<S, TG, B3, 16, true>), grid, block, 0, c->stream, *p, n, d_inp, fstride, d_lines, o, ostride, min_tier, rank, (const int *) perm, 0, 0, fsa); } while (0)
                 /* tier groups as in crt_run_decode: 0 = tiers 0 / 1 (tier 1 only ever holds lines of the 5-sample system here), 1 = 2 / 3 */
                 if (p->out_bpp == 3) {
                     if (min_tier <= 1) CRTHIP_LAUNCH_BLOOM(0, true);

@@ -129,6 +129,117 @@ __device__ __forceinline__ void eq_step64_yiq(Eq64 &y, Eq64 &ci_, Eq64 &cq_, con
     cq = hi32(cq_.hi3);
 }
 
+/*
+ * (r7) The same four cascades as FLOAT stages: v_sub_f32 + v_fma_f32 per stage, both at the full issue rate, no re-arming move, single
+ * registers (host half: crthip_float_stages_query, crt_setup.c).  The wave runs in round-toward-minus-infinity
+ * (fstage_round_down).  A state is a float holding x + bias inside [2^23, 2^24): ulp 1, bit pattern 0x4B000000 + (x + bias - 2^23), so
+ * biasing and un-biasing are integer adds on the bits.  With ce = +-2^k * odd, a = +-2^(15 - k), n = (odd - 1) / 2:
+ *     (ce * d + 2^15) >> 16 == floor(ce * (d + a) / 2^16) - n                          (ce * a / 2^16 = n + 1/2)
+ *   x-form (chroma, ce = c < 2^15):   X' = fma(U - X, ce / 2^16, X)   with bias(U) - bias(X) = a:  X' = x' + bias(X) + n
+ *   u-form (luma, ce = c - 2^16):     X' = fma(U - X, ce / 2^16, U)                                X' = x' + bias(U) + n
+ * -- the difference is exact (integers below 2^24), the product inside the fma is exact, and the one rounding at ulp 1 IS the floor.
+ * So every bias of a cascade moves by a wave-uniform integer per sample; the kernel adds it to two scalars per cascade: the bit
+ * offset that biases the input and the one that un-biases stage 3.  Everything else stays integer: only lo3, hi3, i3, q3 and the
+ * 3-deep input histories are un-biased.  The ops are inline asm so that the compiler neither folds nor moves float arithmetic whose
+ * rounding mode it does not know.  The host proves that nothing leaves the binade over a line and says no otherwise.
+ */
+struct EqF { float lo0, lo1, lo2, lo3, hi0, hi1, hi2, hi3; int h0, h1, h2; };
+__device__ __forceinline__ void fstage_round_down(bool on)
+{
+    /* MODE.FP_ROUND, single precision (bits 1:0): 2 = toward minus infinity, 0 = nearest even.  Per-wave state. */
+    __builtin_amdgcn_sched_barrier(0);
+    if (on) asm volatile("s_setreg_imm32_b32 hwreg(HW_REG_MODE, 0, 2), 2\n\ts_nop 1" ::: "memory");
+    else asm volatile("s_setreg_imm32_b32 hwreg(HW_REG_MODE, 0, 2), 0\n\ts_nop 1" ::: "memory");
+    __builtin_amdgcn_sched_barrier(0);
+}
+__device__ __forceinline__ float fbits(int b) { return __int_as_float(b); }
+__device__ __forceinline__ float subf(float a, float b)
+{
+    float r;
+    asm("v_sub_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+/* d * m + acc, m a wave-uniform float bit pattern */
+__device__ __forceinline__ float fmaf_vs(float d, int m_uniform, float acc)
+{
+    float r;
+    asm("v_fma_f32 %0, %1, %2, %3" : "=v"(r) : "v"(d), "s"(m_uniform), "v"(acc));
+    return r;
+}
+/* float(x) + k and +-a * b + k, k a wave-uniform float bit pattern: the biased inputs */
+__device__ __forceinline__ float addf_sv(int k_uniform, float x)
+{
+    float r;
+    asm("v_add_f32 %0, %1, %2" : "=v"(r) : "s"(k_uniform), "v"(x));
+    return r;
+}
+template <bool NEG> __device__ __forceinline__ float fmaf_vvs(float a, float b, int k_uniform)
+{
+    float r;
+    if (NEG) asm("v_fma_f32 %0, %1, -%2, %3" : "=v"(r) : "v"(a), "v"(b), "s"(k_uniform));
+    else asm("v_fma_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "s"(k_uniform));
+    return r;
+}
+/* the integer a biased float holds: bits - k */
+__device__ __forceinline__ int unbias(float x, int k_uniform)
+{
+    int r;
+    asm("v_subrev_u32 %0, %1, %2" : "=v"(r) : "s"(k_uniform), "v"(x));
+    return r;
+}
+/* float of byte K of a dword, signed: one SDWA conversion */
+__device__ __forceinline__ float cvt_sbyte(int word, int k)
+{
+    float r;
+    if (k == 0) asm("v_cvt_f32_i32_sdwa %0, sext(%1) dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_0" : "=v"(r) : "v"(word));
+    else if (k == 1) asm("v_cvt_f32_i32_sdwa %0, sext(%1) dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_1" : "=v"(r) : "v"(word));
+    else if (k == 2) asm("v_cvt_f32_i32_sdwa %0, sext(%1) dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_2" : "=v"(r) : "v"(word));
+    else asm("v_cvt_f32_i32_sdwa %0, sext(%1) dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_3" : "=v"(r) : "v"(word));
+    return r;
+}
+__device__ __forceinline__ void eqf_reset(EqF &f, int x0, int dstage)
+{
+    f.lo0 = f.hi0 = fbits(x0); f.lo1 = f.hi1 = fbits(x0 + dstage); f.lo2 = f.hi2 = fbits(x0 + 2 * dstage); f.lo3 = f.hi3 = fbits(x0 + 3 * dstage);
+    f.h0 = f.h1 = f.h2 = 0;
+}
+/* One sample through the four cascades, side by side like eq_step64_yiq.  y.lo* / y.hi*: luma low / high (u-form); ci_.hi*, cq_.hi*:
+ * I / Q high (x-form).  uyl, uyh, ui, uq: the inputs with the cascades' input biases; m*: ce / 2^16; ko*: bit offsets of stage 3
+ * after this sample; kyl, ki: bit offsets of the inputs uyl, ui (for the histories). */
+template <int G1, int G2>
+__device__ __forceinline__ void eq_stepf_yiq(EqF &y, EqF &ci_, EqF &cq_, const int myl, const int myh, const int mi, const int mq,
+                                             const float uyl, const float uyh, const float ui, const float uq,
+                                             const int kyl, const int ki, const int koyl, const int koyh, const int koi, const int koq,
+                                             int &cy, int &ci, int &cq)
+{
+#define EQF_PIN() __builtin_amdgcn_sched_barrier(0)
+    float d0 = subf(uyl, y.lo0), d1 = subf(uyh, y.hi0), d2 = subf(ui, ci_.hi0), d3 = subf(uq, cq_.hi0);
+    EQF_PIN();
+    y.lo0 = fmaf_vs(d0, myl, uyl); y.hi0 = fmaf_vs(d1, myh, uyh); ci_.hi0 = fmaf_vs(d2, mi, ci_.hi0); cq_.hi0 = fmaf_vs(d3, mq, cq_.hi0);
+    EQF_PIN();
+#define EQF_STAGES(P, N)                                                                                                         \
+    d0 = subf(y.lo##P, y.lo##N); d1 = subf(y.hi##P, y.hi##N); d2 = subf(ci_.hi##P, ci_.hi##N); d3 = subf(cq_.hi##P, cq_.hi##N);   \
+    EQF_PIN();                                                                                                                   \
+    y.lo##N = fmaf_vs(d0, myl, y.lo##P); y.hi##N = fmaf_vs(d1, myh, y.hi##P);                                                    \
+    ci_.hi##N = fmaf_vs(d2, mi, ci_.hi##N); cq_.hi##N = fmaf_vs(d3, mq, cq_.hi##N);                                              \
+    EQF_PIN();
+    EQF_STAGES(0, 1)
+    EQF_STAGES(1, 2)
+    EQF_STAGES(2, 3)
+#undef EQF_STAGES
+#undef EQF_PIN
+    const int lo3 = unbias(y.lo3, koyl), hi3 = unbias(y.hi3, koyh);
+    int r;
+    if (G1 == 8192) r = lo3 + ((hi3 - lo3) >> 3);                      /* luma envelope, see eq_step64_yiq */
+    else r = ((lo3 * 65536) >> 16) + (__mul24(hi3 - lo3, G1) >> 16);
+    r += __mul24(y.h2 - hi3, G2) >> 16;
+    y.h2 = y.h1; y.h1 = y.h0; y.h0 = unbias(uyl, kyl);
+    cy = r;
+    const int i3 = unbias(ci_.hi3, koi);
+    ci = i3 + (__mul24(ci_.h2 - i3, 1311) >> 16);
+    ci_.h2 = ci_.h1; ci_.h1 = ci_.h0; ci_.h0 = unbias(ui, ki);
+    cq = unbias(cq_.hi3, koq);
+}
+
 /* eqf of a USE_CONVOLUTION build of the reference (crt_core.c:119-147): a symmetric FIR kernel over a 7-deep
  * input history.  The four kernels factor into running sums,
  *     4 taps  1 1 1 1        = box4
@@ -203,12 +314,16 @@ __device__ __forceinline__ unsigned unpack_selector(int format)
 #else
 #define DEC_OCCUPANCY_ATTR
 #endif
-template <class S, int TG, bool BPP3, int PXT, bool BLOOM = false>
+/* FSTAGE (tier group 0 of the 4-sample systems only): the filter stages of tiers 0 and 1 as float sub + fma (eq_stepf_yiq), with
+ * the carrier products (s * wave) >> 9 as one fma each -- exact for every carrier of tier 1, so the two tiers are one loop there.
+ * FS: the host's constants (crthip_float_stages_query); launched only where its verdict is yes. */
+template <class S, int TG, bool BPP3, int PXT, bool BLOOM = false, bool FSTAGE = false>
 __global__ void __launch_bounds__(64) DEC_OCCUPANCY_ATTR
 k_decode(const crthip_params P, int n_fields, const signed char *__restrict__ inp, size_t fstride,
          const crthip_line *__restrict__ lines, unsigned char *__restrict__ outp, size_t ostride, int min_tier,
-         int want_rank, const int *__restrict__ perm, int order_k, int order_per)
+         int want_rank, const int *__restrict__ perm, int order_k, int order_per, const FStageArgs FS)
 {
+    static_assert(!FSTAGE || (TG == 0 && S::CCS == 4), "float stages: tiers 0 / 1 of the 4-sample systems");
     constexpr int TLO = 2 * TG;
     constexpr int IN_TILE_DW = DEC_IN_TILE_DW, IN_PIECES = IN_TILE_DW / 4;
     using TIN = TileRows<IN_TILE_DW>;                 /* row addressing of both tiles: conflict-free lane-per-row AND cooperatively (crt_dev.h) */
@@ -252,6 +367,7 @@ k_decode(const crthip_params P, int n_fields, const signed char *__restrict__ in
     constexpr bool FAST = TIER <= 2 || TIER == 4;   /* 24-bit multiplies outside the filter stages */
     constexpr bool FIR = TIER >= 4;
     int nrows_todo = nrows;
+    if (FSTAGE) fstage_round_down(true);            /* nothing but the stages' own inline asm computes in floats below */
   do {
     int scanl_u = 0, dx_u = P.dx;
     if (BLOOM) {
@@ -301,6 +417,14 @@ k_decode(const crthip_params P, int n_fields, const signed char *__restrict__ in
     /* tier 0 multipliers: luma coefficients are 2^16 + c', chroma ones < 2^15 (host-checked) */
     const int ylfm = (ylf - 65536) << 16, yhfm = (yhf - 65536) << 16;
     const int ihfm = ihf << 16, qhfm = qhf << 16;              /* (the chroma low cascades are not computed in these tiers) */
+    /* float stages: state, the carriers / 512 (exact), the running bit offsets of inputs and outputs (wave-uniform) */
+    EqF gy, gi, gq;
+    eqf_reset(gy, FS.x0[0], FS.dstage[0]);
+    gy.hi0 = fbits(FS.x0[1]); gy.hi1 = fbits(FS.x0[1] + FS.dstage[1]); gy.hi2 = fbits(FS.x0[1] + 2 * FS.dstage[1]); gy.hi3 = fbits(FS.x0[1] + 3 * FS.dstage[1]);
+    eqf_reset(gi, FS.x0[2], FS.dstage[2]); eqf_reset(gq, FS.x0[3], FS.dstage[3]);
+    const float wf0 = (float) lp.wave0 * (1.0f / 512.0f), wf1 = (float) lp.wave1 * (1.0f / 512.0f);
+    int kin0 = FS.in0[0], kin1 = FS.in0[1], kin2 = FS.in0[2], kin3 = FS.in0[3];
+    int kout0 = FS.out0[0], kout1 = FS.out0[1], kout2 = FS.out0[2], kout3 = FS.out0[3];
     int py = 0, pi = 0, pq = 0;                    /* yiq of the previous sample */
 
     /* wave-uniform output pixel schedule, crt_core.c:528-531,555-562 */
@@ -364,7 +488,21 @@ k_decode(const crthip_params P, int n_fields, const signed char *__restrict__ in
                 }
                 if (BLOOM && x < first) continue;  /* wave-uniform: the filters start at scanL >> 12, crt_core.c:539 */
                 int cy, ci, cq;
-                if (TIER == 0) {
+                if (FSTAGE) {
+                    /* the sample as a float (one SDWA conversion), luma inputs = s + bright + bias (the offset carries bright),
+                     * chroma inputs = floor(s * wave / 512) + bias: the fma's one rounding, -wave by its neg modifier */
+                    const float fs = cvt_sbyte(word, k);
+                    const float uyl = addf_sv(kin0 + bright, fs), uyh = addf_sv(kin1 + bright, fs);
+                    const float ui = k == 0 ? fmaf_vvs<false>(fs, wf0, kin2) : k == 1 ? fmaf_vvs<false>(fs, wf1, kin2)
+                                   : k == 2 ? fmaf_vvs<true>(fs, wf0, kin2) : fmaf_vvs<true>(fs, wf1, kin2);
+                    const float uq = k == 0 ? fmaf_vvs<true>(fs, wf1, kin3) : k == 1 ? fmaf_vvs<false>(fs, wf0, kin3)
+                                   : k == 2 ? fmaf_vvs<false>(fs, wf1, kin3) : fmaf_vvs<true>(fs, wf0, kin3);
+                    eq_stepf_yiq<GY1, GY2>(gy, gi, gq, FS.mul[0], FS.mul[1], FS.mul[2], FS.mul[3], uyl, uyh, ui, uq,
+                                           kin0, kin2, kout0, kout1, kout2, kout3, cy, ci, cq);
+                    ci >>= 3; cq >>= 3;
+                    kin0 += FS.drift[0]; kin1 += FS.drift[1]; kin2 += FS.drift[2]; kin3 += FS.drift[3];
+                    kout0 += FS.drift[0]; kout1 += FS.drift[1]; kout2 += FS.drift[2]; kout3 += FS.drift[3];
+                } else if (TIER == 0) {
                     /* luma stays unshifted here: (y << 4) * w >> 2 == (y * w) << 2 while nothing wraps, see D9 */
                     eq_step64_yiq<GY1, GY2>(wy, wi_, wq_, ylfm, yhfm, ihfm, qhfm, pair_of(s + bright), __mul24(s, wi), __mul24(s, wq), cy, ci, cq);
                     ci >>= 3; cq >>= 3;                        /* wi, wq: carriers << 7 here */
@@ -523,8 +661,9 @@ k_decode(const crthip_params P, int n_fields, const signed char *__restrict__ in
     }
     wave_lds_fence();
   } while (BLOOM && __ballot(nrows_todo > 0) != 0ull);
+    if (FSTAGE) fstage_round_down(false);
   };
-    if (tier == TLO) decode_lines(std::integral_constant<int, TLO>{});
+    if (FSTAGE || tier == TLO) decode_lines(std::integral_constant<int, TLO>{});
     else decode_lines(std::integral_constant<int, TLO + 1>{});
 }
 

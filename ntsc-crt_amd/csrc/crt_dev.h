@@ -240,6 +240,10 @@ __device__ __forceinline__ int line_tier_flags(int wave0, int wave1, int saturat
     return f;
 }
 
+/* kernel argument of the float filter stages (k_decode<..., FSTAGE = true>): what crthip_float_stages_query computed, by cascade
+ * (0 luma low, 1 luma high, 2 I high, 3 Q high).  All float bit patterns but `drift` and `dstage`, which are added to them. */
+struct FStageArgs { int mul[4], x0[4], dstage[4], in0[4], out0[4], drift[4]; };
+
 typedef int v4i __attribute__((ext_vector_type(4)));
 struct __attribute__((packed)) unaligned16 { v4i v; };
 struct __attribute__((packed)) unaligned4 { int v; };
@@ -566,6 +570,9 @@ struct crthip_ctx {
     sig_layout still_lay;
     int wide_order_env, dec_order_env, act_order_env;   /* CRTHIP_WIDE_ORDER / _DEC_ORDER / _ACT_ORDER: workgroup order of k_decode_wide / k_decode / k_active
                                                            (block_item above): 0 = the default, K > 1 = that many strides, -1 = one stride per field, 1 = in order */
+    int dec_float;              /* CRTHIP_DEC_FLOAT: 1 (default) = k_decode's tiers 0 / 1 run their filter stages as float sub + fma where
+                                   crthip_float_stages_query says yes (crt_decode_lane.h, eq_stepf_yiq), 0 = the integer stages (A/B switch) */
+    int last_fstage;            /* the last decoder call launched the float-stage kernels (crthip_float_stages_used) */
     int sig_tile_env;           /* CRTHIP_SIG_TILE = 16 | 32 | 64: pins k_active's small / large signal tile (A/B measurements); 0 = by batch size */
     int overlap_chunks;         /* crthip_fieldpass: chunks alternating between two streams (1 = off) */
     hipStream_t aux_stream;
@@ -697,6 +704,7 @@ int crt_run_decode(crthip_ctx *c, const crthip_params *p, int n, const signed ch
                    const crthip_line *d_lines, void *d_out, size_t ostride, size_t fstride = 0);   /* fstride 0: the flat layout's */
 int crt_decode_check(crthip_ctx *c, const crthip_params *p);
 bool crt_decode_wide_ok(const crthip_ctx *c, const crthip_params *p, int min_tier, bool wide);
+bool crt_decode_fstages(crthip_ctx *c, const crthip_params *p, int min_tier, FStageArgs *fs);   /* crt_decode.hip */
 int crt_run_decode_wide(crthip_ctx *c, const crthip_params *p, int n, const signed char *d_inp, const crthip_line *d_lines,
                         void *d_out, size_t ostride, int min_tier, int rank, size_t fstride);
 int crt_reserve_bloom(crthip_ctx *c, int n);

@@ -623,6 +623,7 @@ int crthip_create(crthip_ctx **out, int device, int system, int chroma_pattern)
     { const char *e = getenv("CRTHIP_WIDE_ORDER"); c->wide_order_env = e ? atoi(e) : 0; }   /* A/B switches: workgroup order (crt_dev.h, block_item) */
     { const char *e = getenv("CRTHIP_DEC_ORDER"); c->dec_order_env = e ? atoi(e) : 0; }
     { const char *e = getenv("CRTHIP_ACT_ORDER"); c->act_order_env = e ? atoi(e) : 0; }
+    { const char *e = getenv("CRTHIP_DEC_FLOAT"); c->dec_float = e ? atoi(e) != 0 : 1; c->last_fstage = 0; }   /* A/B switch: float filter stages in k_decode (crt_decode_lane.h) */
     { const char *e = getenv("CRTHIP_SIG_TILE"); c->sig_tile_env = e && (atoi(e) == 16 || atoi(e) == 32 || atoi(e) == 64) ? atoi(e) : 0; }   /* A/B switch, k_active */
     c->own_stream = false;
     /* noise LCG jump tables: state after 16*q steps, q = 0 .. INPUT_SIZE/16 */
@@ -1201,6 +1202,8 @@ int crthip_signal_layout_query(const crthip_params *p, int n_fields, int shape, 
     if (field_stride) *field_stride = lay.fstride;
     return padded ? 1 : 0;
 }
+
+int crthip_float_stages_used(const crthip_ctx *c) { return c ? c->last_fstage : CRTHIP_E_ARG; }
 
 int crthip_set_signal_layout(crthip_ctx *c, int padded)
 {

@@ -797,3 +797,103 @@ crt_setup_vhs_power_table(unsigned long first, unsigned long step, int count, un
         poly_mul_mod(rows + 31 * (q - 1), stepc, rows + 31 * q);
     }
 }
+
+/*
+ * The float form of the decoder's filter stages (crt_hip.h): per cascade the rounding pair (a, n), the bias
+ * schedule and the proof that nothing leaves the binade [2^23, 2^24) over `steps` samples.
+ *   states:  |x_j| <= M_j.  0 < alpha = c / 2^16 <= 1: a stage output lies between its state and its input (round-to-nearest of
+ *            alpha * d never exceeds the integer |d|), M_j = M_in.  alpha > 1 overshoots: x' = (1 - alpha) x + alpha u + r,
+ *            |r| <= 1/2, so M_j = (alpha M_(j-1) + 1) / (1 - |1 - alpha|) + 1 (the bound decoder_min_tier uses).
+ *   inputs:  luma |s + bright| <= 128 + |bright|; chroma |(s * wave) >> 9| <= 128 * 120000 / 512 + 1 (tiers 0 / 1).
+ *   biases are linear in the sample index, so the extremes are at the line's two ends.
+ */
+#define FSTAGE_WAVE_MAX 120000L                     /* T0_WAVE_MAX, crt_dev.h */
+static int
+fstage_bits(double v)
+{
+    return (int) (0x4B000000L + (long) (v - 8388608.0));
+}
+
+int
+crthip_float_stages_query(const crthip_params *p, int steps, crthip_fstages *out)
+{
+    struct crt_sysdef d;
+    int k, j, t, ok = 1;
+    long b;
+
+    if (!p || !out || p->finalized != CRTHIP_PARAMS_MAGIC || steps < 0 ||
+        crt_sysdef_get(&d, p->system, p->chroma_pattern) != CRTHIP_OK) {
+        return CRTHIP_E_ARG;
+    }
+    memset(out, 0, sizeof *out);
+    if (steps == 0) steps = d.av_len + 1;
+    out->steps = steps;
+    b = p->bright < 0 ? -(long) p->bright : (long) p->bright;
+    if (b > 130000L) ok = 0;                        /* FAST_BRIGHT_MAX: beyond it no fast tier runs at all */
+    for (k = 0; k < 4; k++) {
+        crthip_fstage_cascade *q = &out->cas[k];
+        int c = k == 0 ? p->eq_lf[0] : k == 1 ? p->eq_hf[0] : k == 2 ? p->eq_hf[1] : p->eq_hf[2];
+        int ce, odd, sh = 0, cas_ok = 1;
+        double m_in, m, lo, hi, x0, span;
+        float mul;
+
+        q->c = c;
+        q->form = k < 2;
+        if (q->form ? (c < 32768 || c >= 98304) : (c <= 0 || c >= 32768)) cas_ok = 0;
+        ce = q->form ? c - 65536 : c;
+        q->ce = ce;
+        if (ce == 0) cas_ok = 0;                    /* alpha = 1 exactly: no odd part */
+        if (!cas_ok) {
+            ok = 0;
+            continue;
+        }
+        odd = ce < 0 ? -ce : ce;
+        while (!(odd & 1)) {
+            odd >>= 1;
+            sh++;
+        }                                           /* |ce| <= 2^15: sh <= 15 */
+        q->a = ce < 0 ? -(1 << (15 - sh)) : 1 << (15 - sh);
+        q->n = (odd - 1) / 2;
+        q->drift = q->form ? q->n + q->a : q->n;
+        q->dstage = q->form ? q->n : q->n - q->a;
+        mul = (float) ce / 65536.0f;                /* exact: |ce| < 2^24, a power-of-two divisor */
+        memcpy(&q->mul_bits, &mul, sizeof q->mul_bits);
+        m_in = k < 2 ? 128.0 + (double) b : (double) (128L * FSTAGE_WAVE_MAX / 512L + 1L);
+        q->in_max = (int) m_in;
+        /* range of input and states relative to the bias of stage 0 at sample 0 */
+        lo = hi = 0.0;
+        for (t = 0; t < 2; t++) {
+            const double at = (double) q->drift * (t ? (double) steps : 0.0);
+            if (at + q->a - m_in < lo) lo = at + q->a - m_in;
+            if (at + q->a + m_in > hi) hi = at + q->a + m_in;
+        }
+        m = m_in;
+        for (j = 0; j < 4; j++) {
+            const double al = (double) c / 65536.0;
+            if (al > 1.0) m = (al * m + 1.0) / (1.0 - (al - 1.0)) + 1.0;
+            for (t = 0; t < 2; t++) {
+                const double at = (double) q->drift * (t ? (double) steps : 0.0) + (double) q->dstage * j;
+                if (at - m < lo) lo = at - m;
+                if (at + m > hi) hi = at + m;
+            }
+        }
+        q->state_max = m < 2147483647.0 ? (int) m + 1 : 2147483647;
+        lo = (double) (long) lo - 1.0;              /* whole numbers, outwards (the overshoot bound is no integer) */
+        hi = (double) (long) hi + 1.0;
+        span = hi - lo;
+        if (span > 8388608.0 - 4.0) {
+            ok = 0;
+            continue;
+        }
+        x0 = 8388608.0 + (double) (long) ((8388608.0 - span) / 2.0) - lo;      /* centred in the binade */
+        q->lo = (int) (x0 + lo);
+        q->hi = (int) (x0 + hi);
+        q->x0_bits = fstage_bits(x0);
+        q->in0_bits = fstage_bits(x0 + q->a);
+        q->out0_bits = fstage_bits(x0 + 3.0 * q->dstage + q->drift);
+    }
+    out->ranges_ok = ok;
+    if (d.cc_samples != 4) ok = 0;                  /* k_decode's float loop is the 4-sample one */
+    out->ok = ok;
+    return ok;
+}

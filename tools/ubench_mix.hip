@@ -185,6 +185,67 @@ __global__ void k_stage16_dot2(int *out, int c, int u)
     out[blockIdx.x * blockDim.x + threadIdx.x] = r0 ^ r1 ^ r2 ^ r3 ^ r4;
 }
 
+// the float form of the same stage: state = float(x + bias) with ulp 1, the wave in round-toward-minus-infinity,
+// x' = fma(u - x, c / 65536, x) -- v_sub_f32 + v_fma_f32, no re-arming move, single registers.  Four independent cascades,
+// grouped by opcode (the order of eq_stepf_yiq); the values stay near 2^23, so both instructions see real mantissas
+#define SUBF(d, a, b) asm volatile("v_sub_f32 %0, %1, %2" : "=v"(d) : "v"(a), "v"(b))
+#define FMAF(x, d, m) asm volatile("v_fma_f32 %0, %1, %2, %0" : "+v"(x) : "v"(d), "s"(m))
+#define FMAFU(x, d, m, u) asm volatile("v_fma_f32 %0, %1, %2, %3" : "=v"(x) : "v"(d), "s"(m), "v"(u))
+__device__ __forceinline__ void round_down(bool on)
+{
+    if (on) asm volatile("s_setreg_imm32_b32 hwreg(HW_REG_MODE, 0, 2), 2");
+    else asm volatile("s_setreg_imm32_b32 hwreg(HW_REG_MODE, 0, 2), 0");
+}
+__global__ void k_stagef_grp(int *out, int c, int u)
+{
+    float x0 = 8388608.0f + 4096.0f + threadIdx.x, x1 = x0 + 1, x2 = x0 + 2, x3 = x0 + 3, d0, d1, d2, d3;
+    const float vu = 8388608.0f + 4096.0f + 8192.0f + (u + (threadIdx.x & 3)), m = c * 4079.0f / 65536.0f;
+    round_down(true);
+    for (int i = 0; i < ITERS; i++) {
+        SUBF(d0, vu, x0); SUBF(d1, vu, x1); SUBF(d2, vu, x2); SUBF(d3, vu, x3);
+        FMAF(x0, d0, m); FMAF(x1, d1, m); FMAF(x2, d2, m); FMAF(x3, d3, m);
+    }
+    round_down(false);
+    out[blockIdx.x * blockDim.x + threadIdx.x] = __float_as_int(x0) ^ __float_as_int(x1) ^ __float_as_int(x2) ^ __float_as_int(x3);
+}
+// ... and four stages of ONE cascade after each other (every instruction reads the one before it)
+__global__ void k_stagef_seq(int *out, int c, int u)
+{
+    float x0 = 8388608.0f + 4096.0f + threadIdx.x, x1 = x0 + 1, x2 = x0 + 2, x3 = x0 + 3, d;
+    const float vu = 8388608.0f + 4096.0f + 8192.0f + (u + (threadIdx.x & 3)), m = c * 4079.0f / 65536.0f;
+    round_down(true);
+    for (int i = 0; i < ITERS; i++) {
+        SUBF(d, vu, x0); FMAF(x0, d, m);
+        SUBF(d, x0, x1); FMAF(x1, d, m);
+        SUBF(d, x1, x2); FMAF(x2, d, m);
+        SUBF(d, x2, x3); FMAF(x3, d, m);
+    }
+    round_down(false);
+    out[blockIdx.x * blockDim.x + threadIdx.x] = __float_as_int(x0) ^ __float_as_int(x1) ^ __float_as_int(x2) ^ __float_as_int(x3);
+}
+// ... and a whole sample's worth as the decoder runs it: four cascades side by side, four stages deep, the luma pair in the
+// u-form (the addend is the stage's input): 32 instructions per iteration against the 48 of four stage64_grp rounds
+__global__ void k_stagef_yiq(int *out, int c, int u)
+{
+    float a0 = 8388608.0f + 4096.0f + threadIdx.x, a1 = a0 + 1, a2 = a0 + 2, a3 = a0 + 3;
+    float b0 = a0 + 4, b1 = a0 + 5, b2 = a0 + 6, b3 = a0 + 7, i0 = a0 + 8, i1 = a0 + 9, i2 = a0 + 10, i3 = a0 + 11;
+    float q0 = a0 + 12, q1 = a0 + 13, q2 = a0 + 14, q3 = a0 + 15, d0, d1, d2, d3;
+    const float vu = 8388608.0f + 4096.0f + 8192.0f + (u + (threadIdx.x & 3)), m = c * 4079.0f / 65536.0f, ml = -c * 2922.0f / 65536.0f;
+    round_down(true);
+    for (int i = 0; i < ITERS; i++) {
+        SUBF(d0, vu, a0); SUBF(d1, vu, b0); SUBF(d2, vu, i0); SUBF(d3, vu, q0);
+        FMAFU(a0, d0, ml, vu); FMAFU(b0, d1, ml, vu); FMAF(i0, d2, m); FMAF(q0, d3, m);
+        SUBF(d0, a0, a1); SUBF(d1, b0, b1); SUBF(d2, i0, i1); SUBF(d3, q0, q1);
+        FMAFU(a1, d0, ml, a0); FMAFU(b1, d1, ml, b0); FMAF(i1, d2, m); FMAF(q1, d3, m);
+        SUBF(d0, a1, a2); SUBF(d1, b1, b2); SUBF(d2, i1, i2); SUBF(d3, q1, q2);
+        FMAFU(a2, d0, ml, a1); FMAFU(b2, d1, ml, b1); FMAF(i2, d2, m); FMAF(q2, d3, m);
+        SUBF(d0, a2, a3); SUBF(d1, b2, b3); SUBF(d2, i2, i3); SUBF(d3, q2, q3);
+        FMAFU(a3, d0, ml, a2); FMAFU(b3, d1, ml, b2); FMAF(i3, d2, m); FMAF(q3, d3, m);
+    }
+    round_down(false);
+    out[blockIdx.x * blockDim.x + threadIdx.x] = __float_as_int(a3) ^ __float_as_int(b3) ^ __float_as_int(i3) ^ __float_as_int(q3);
+}
+
 template <class K> void run(const char *name, K kern, int *d, int per_iter)
 {
     hipEvent_t e0, e1; (void) hipEventCreate(&e0); (void) hipEventCreate(&e1);
@@ -218,5 +279,8 @@ int main()
     run("stage16_pk", k_stage16_pk, d, 10);          // 4 stages in 10 instructions: multiply cycles/instr by 10 (vs 12 for stage64_*)
     run("stage16_sdwa", k_stage16_sdwa, d, 10);
     run("stage16_dot2", k_stage16_dot2, d, 12);
+    run("stagef_grp", k_stagef_grp, d, 8);           // 4 stages in 8 instructions: multiply cycles/instr by 8 (vs 12 for stage64_*)
+    run("stagef_seq", k_stagef_seq, d, 8);
+    run("stagef_yiq", k_stagef_yiq, d, 32);          // 16 stages in 32 instructions (four stage64_grp rounds: 48)
     return 0;
 }
