@@ -270,6 +270,43 @@ int  crthip_fieldpass(crthip_ctx *ctx, const crthip_params *p, int n,
                       crthip_state *d_state);
 
 /*
+ * PER-FIELD KNOBS: a batch whose fields differ in channel noise, monitor hue and saturation -- what the reference's interactive
+ * driver changes from one field to the next (crt_main.c:351-391) and crt_demodulate reads afresh in every call
+ * (crt_core.c:318-320, 362, 476-477).  The other members of crthip_params stay uniform over the batch.
+ *
+ * crthip_knobs_prepare (host only): recs[k] = what the kernels read for field k -- huesn / huecs exactly as crthip_params_finalize
+ * derives them from mon_hue (crt_core.c:318-320), bloom_max_e for the field's noise (crt_core.c:400) -- and env = the batch-wide
+ * bounds the library otherwise takes from the uniform values: the largest |noise| (the encoder's 24-bit envelope), the largest
+ * |saturation|, and the decoder's no-low-cascade bound (crthip_params.loskip_wave_max) for the widest signal range any field's
+ * noise gives.  p must be finalized; p->noise, p->mon_hue and p->saturation are ignored.  CRTHIP_E_ARG: p not finalized, n <= 0, a
+ * NULL pointer, or a field whose knobs crthip_params_finalize would refuse in p (bloom builds: noise < 0 or max_e <= 0).
+ *
+ * crthip_fieldpass_knobs: bit for bit and state for state what n calls of crthip_fieldpass with n = 1 give, call k on field k's
+ * slice of d_images, d_out and d_state with p->noise, p->mon_hue and p->saturation replaced by field k's knobs (a field with noise 0
+ * inside a noisy batch advances rn like every other).  d_recs: the n records of crthip_knobs_prepare, uploaded by the caller (DEVICE
+ * memory, read when the kernels run: a captured graph reads what the buffer holds at replay -- and keeps the bounds of the env it
+ * was captured with, so records written later must stay inside them); env: the same call's bounds, host.
+ * Everything crthip_fieldpass accepts is accepted with the same meaning (bloom, FIR, the phosphor flags, both kernel shapes and
+ * signal layouts, the overlap chunks, the rand()-noise VHS build), what it refuses is refused, and so are env->magic / env->n that
+ * do not match and both phosphor flags at once (CRTHIP_E_ARG; d_out and d_state untouched).  Like crthip_fieldpass after
+ * crthip_reserve it allocates nothing, does not synchronise and can be captured; crthip_fieldpass_signal works after it.
+ * Records that do not come from the prepare call that made env (larger noise, larger |saturation|) give unspecified pictures -- but
+ * no access outside the buffers: the knobs only enter arithmetic, never an address.
+ * REFUSED: CRTHIP_SYSTEM_PV1K.  The 5-sample decoder rotates its carriers by the monitor hue and scales them by the saturation in
+ * its own prologue, from crthip_params (crt_core.c:497-505: ((dci * cos + dcq * sin) >> 15) * saturation -- the shift in front of
+ * the product keeps the sync kernel from folding either in exactly).
+ */
+typedef struct crthip_knobs     { int noise, mon_hue, saturation, reserved; } crthip_knobs;                                /* 16 bytes */
+typedef struct crthip_knob_rec  { int noise, huesn, huecs, saturation, bloom_max_e, reserved[3]; } crthip_knob_rec;        /* 32 bytes */
+typedef struct crthip_knobs_env { int magic, n, noise_max, sat_abs_max, loskip_wave_max, reserved[3]; } crthip_knobs_env;
+int  crthip_knobs_prepare(const crthip_params *p, int n, const crthip_knobs *knobs,
+                          crthip_knob_rec *recs /* n, host, out */, crthip_knobs_env *env);
+int  crthip_fieldpass_knobs(crthip_ctx *ctx, const crthip_params *p, int n,
+                            const void *d_images, size_t image_stride, void *d_out, size_t out_stride,
+                            crthip_state *d_state,
+                            const crthip_knob_rec *d_recs /* n, DEVICE */, const crthip_knobs_env *env /* host */);
+
+/*
  * SEQUENCE mode: n consecutive fields of ONE television set -- what the reference's
  * batch driver does (extra/video_convert.c:246-277:  for every frame: crt_modulate; crt_demodulate;
  * write the output image), with the sync state and the output buffer carried from field to field,

@@ -65,6 +65,26 @@ class Pass(C.Structure):
 STILLS_MAX_PASSES = 64
 
 
+class Knobs(C.Structure):
+    """crthip_knobs (include/crt_hip.h): what varies per field in fieldpass_knobs, as the caller thinks of it."""
+    _fields_ = [("noise", C.c_int), ("mon_hue", C.c_int), ("saturation", C.c_int), ("reserved", C.c_int)]
+
+
+class KnobRec(C.Structure):
+    """crthip_knob_rec (include/crt_hip.h): what the kernels read per field, 32 bytes."""
+    _fields_ = [("noise", C.c_int), ("huesn", C.c_int), ("huecs", C.c_int), ("saturation", C.c_int),
+                ("bloom_max_e", C.c_int), ("reserved", C.c_int * 3)]
+
+
+class KnobsEnv(C.Structure):
+    """crthip_knobs_env (include/crt_hip.h): the batch-wide bounds of one knobs_prepare call."""
+    _fields_ = [("magic", C.c_int), ("n", C.c_int), ("noise_max", C.c_int), ("sat_abs_max", C.c_int),
+                ("loskip_wave_max", C.c_int), ("reserved", C.c_int * 3)]
+
+
+KNOB_REC_INTS = C.sizeof(KnobRec) // 4
+
+
 class Params(C.Structure):
     """crthip_params (include/crt_hip.h)."""
     _fields_ = [(n, C.c_int) for n in (
@@ -176,6 +196,9 @@ def load_library():
     L.crthip_set_pixel_tile.argtypes = [vp, ci]
     L.crthip_profile_read.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(ci)]
     L.crthip_phosphor_table.argtypes = [ci, C.POINTER(C.c_ubyte)]
+    if hasattr(L, "crthip_fieldpass_knobs"):                      # (an earlier build loaded through CRTHIP_LIBDIR for an A/B run has none)
+        L.crthip_knobs_prepare.argtypes = [PP, ci, C.POINTER(Knobs), C.POINTER(KnobRec), C.POINTER(KnobsEnv)]
+        L.crthip_fieldpass_knobs.argtypes = [vp, PP, ci, vp, sz, vp, sz, vp, vp, C.POINTER(KnobsEnv)]
     _LIB = L
     return L
 
@@ -210,6 +233,27 @@ def phosphor_table(age):
     if rc:
         raise ValueError("crthip_phosphor_table failed (%d)" % rc)
     return bytes(lut)
+
+
+def knobs_prepare(params, knobs):
+    """crthip_knobs_prepare (host only): ``knobs`` = (n, 3) integers, one (noise, mon_hue, saturation) per field, for the
+    finalized ``params`` -> (records as an (n, 8) int32 numpy array in the layout of KnobRec, KnobsEnv)."""
+    import numpy as np
+    if hasattr(knobs, "detach"):
+        knobs = knobs.detach().cpu().numpy()
+    k = np.asarray(knobs)
+    if k.ndim != 2 or k.shape[1] != 3 or k.shape[0] < 1 or not np.issubdtype(k.dtype, np.integer):
+        raise ValueError("knobs must be an (n, 3) integer array of (noise, mon_hue, saturation)")
+    n = int(k.shape[0])
+    kin = np.zeros((n, 4), dtype=np.int32)
+    kin[:, :3] = k
+    recs = np.zeros((n, KNOB_REC_INTS), dtype=np.int32)
+    env = KnobsEnv()
+    rc = load_library().crthip_knobs_prepare(C.byref(params), n, kin.ctypes.data_as(C.POINTER(Knobs)),
+                                             recs.ctypes.data_as(C.POINTER(KnobRec)), C.byref(env))
+    if rc:
+        raise ValueError("crthip_knobs_prepare failed (%d)" % rc)
+    return recs, env
 
 
 def stills_schedule(interlaced=True, first_field=0, frames=4):
@@ -283,6 +327,8 @@ class CRT:
         self._inp = None
         self._lines = None
         self._settings = None
+        self.knob_recs = None      # device records of fieldpass_knobs ([n, 8] int32, allocated by the first upload_knobs) and their bounds
+        self._knob_env = None
         self.use_stream(None)
         self.vhs_hist = None
         if self.sysid == SYSTEM_VHS:
@@ -429,6 +475,37 @@ class CRT:
                                      self._image_stride(s), C.c_void_p(self.out.data_ptr()),
                                      self.out.stride(0), C.c_void_p(self.state.data_ptr()))
         self._check(rc, "crthip_fieldpass")
+        s.initialized = 1
+
+    def upload_knobs(self, knobs, params):
+        """knobs_prepare for ``params`` + one copy into this CRT's device record buffer (allocated once, then reused: a captured
+        fieldpass_knobs reads what the buffer holds at replay).  Returns the KnobsEnv, which fieldpass_knobs(s, None) reuses."""
+        torch = self.torch
+        recs, env = knobs_prepare(params, knobs)
+        if recs.shape[0] != self.n:
+            raise ValueError("%d knob triples for a batch of %d fields" % (recs.shape[0], self.n))
+        if self.knob_recs is None:
+            self.knob_recs = torch.zeros((self.n, KNOB_REC_INTS), dtype=torch.int32, device=self.dev)
+        self.knob_recs.copy_(torch.from_numpy(recs))
+        self._knob_env = env
+        return env
+
+    def fieldpass_knobs(self, s, knobs, params=None):
+        """fieldpass with per-field (noise, mon_hue, saturation): ``knobs`` = (n, 3) integer array or tensor (None: the records
+        and bounds of the last upload_knobs -- inside a graph capture, where nothing may be copied from the host).  The batch-
+        uniform rest comes from ``params`` (or this CRT's settings); its own noise, mon_hue and saturation are ignored."""
+        p = params if params is not None else self.params(s, 0)
+        if params is None:
+            self._load_field_state(s)
+        if knobs is not None:
+            self.upload_knobs(knobs, p)
+        if self.knob_recs is None:
+            raise ValueError("fieldpass_knobs(s, None): no knobs uploaded yet (upload_knobs)")
+        rc = self.L.crthip_fieldpass_knobs(self.ctx, C.byref(p), self.n, C.c_void_p(s.data.data_ptr()),
+                                           self._image_stride(s), C.c_void_p(self.out.data_ptr()),
+                                           self.out.stride(0), C.c_void_p(self.state.data_ptr()),
+                                           C.c_void_p(self.knob_recs.data_ptr()), C.byref(self._knob_env))
+        self._check(rc, "crthip_fieldpass_knobs")
         s.initialized = 1
 
     def stills_reserve(self, n_distinct):

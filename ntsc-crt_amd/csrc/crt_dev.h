@@ -343,6 +343,13 @@ __device__ __forceinline__ int mad24_vv(int v, int s_uniform, int acc_v)
     asm("v_mad_i32_i24 %0, %1, %2, %3" : "=v"(r) : "v"(v), "s"(s_uniform), "v"(acc_v));
     return r;
 }
+/* the same with a per-lane multiplier (per-field knobs: the noise gain of the lane's field) */
+__device__ __forceinline__ int mad24_vvv(int v, int m_v, int acc_v)
+{
+    int r;
+    asm("v_mad_i32_i24 %0, %1, %2, %3" : "=v"(r) : "v"(v), "v"(m_v), "v"(acc_v));
+    return r;
+}
 /* v_mad_i64_i32: vgpr * sgpr + 64-bit register pair (used as "multiply, shift and accumulate in one instruction": the
  * state of a one-pole filter lives in the HIGH half of a pair, the multiplier is pre-shifted so that the wanted
  * quotient bits land there; see eq_step64_yiq in crt_decode_lane.h and the encoder's low-passes in crt_encode.hip) */
@@ -420,6 +427,21 @@ __device__ __forceinline__ unsigned lcg_at(const uint2 *__restrict__ jump16, uns
     unsigned rn = j.x * rn0 + j.y;
     for (int k = idx & 15; k > 0; k--) rn = lcg_step(rn);
     return rn;
+}
+
+/* Per-field knobs (crthip_fieldpass_knobs).  The kernels that apply the channel noise or fold the monitor hue and saturation into the
+ * line table have a second instantiation, KN, that takes the value from the field's crthip_knob_rec instead of the parameter blob.
+ * Their signatures do not change: the blob a knob launch passes is the library's own copy, whose `reserved` words carry the device
+ * pointer to the record of the launch's field 0 (crt_host.hip, fieldpass_chunk), and whose noise / saturation are the batch's
+ * bounds -- what the launch code decides by.  crthip_ctx.knob_recs != nullptr says that such a call is under way. */
+static inline void knob_blob_set(crthip_params *q, const crthip_knob_rec *d_recs)
+{
+    static_assert(sizeof(q->reserved) == sizeof(d_recs), "a device pointer fits crthip_params.reserved");
+    memcpy(q->reserved, &d_recs, sizeof(d_recs));
+}
+__device__ __forceinline__ const crthip_knob_rec *knob_blob_recs(const crthip_params &P)
+{
+    return (const crthip_knob_rec *) (((unsigned long long) (unsigned) P.reserved[1] << 32) | (unsigned) P.reserved[0]);
 }
 
 /* fields per launch up to which the scanline-parallel kernel shapes are chosen automatically: lane-per-scanline needs
@@ -575,6 +597,8 @@ struct crthip_ctx {
     int last_fstage;            /* the last decoder call launched the float-stage kernels (crthip_float_stages_used) */
     int sig_tile_env;           /* CRTHIP_SIG_TILE = 16 | 32 | 64: pins k_active's small / large signal tile (A/B measurements); 0 = by batch size */
     int overlap_chunks;         /* crthip_fieldpass: chunks alternating between two streams (1 = off) */
+    const crthip_knob_rec *knob_recs;   /* crthip_fieldpass_knobs under way: the caller's device records (field 0 of the batch), else nullptr */
+    int knob_loskip;            /* ... and its crthip_knobs_env.loskip_wave_max */
     hipStream_t aux_stream;
     hipEvent_t ev_fork, ev_join, ev_chunk[CRTHIP_MAX_CHUNKS];
     hipEvent_t ev_mfork, ev_mjoin;   /* the margin kernel beside the active-video kernel (crt_encode.hip, launch_encoder) */

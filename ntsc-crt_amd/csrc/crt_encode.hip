@@ -431,7 +431,9 @@ template <class S> __device__ __forceinline__ int source_row(const crthip_params
  * small; 64 (256-byte pieces, 16.6 KB) is what large batches take: the encoder is bound by its MEMORY PATTERN -- image pieces in,
  * signal pieces out, no arithmetic at all reproduces its time (tools/ubench_enc.hip, profiles/r05_encoder_memory_shapes.txt) -- and
  * 64-byte pieces at the reference's odd line starts are its dearest part */
-template <class S, bool NOISE, bool FAST, bool IN4, bool CLAMP, int ACT, int OT = 16, int OL = OT>
+/* KN: the noise gain is the one of the lane's field (crthip_knob_rec, crt_dev.h) -- one more per-lane load beside state[f], and a
+ * vector register where the uniform instantiations multiply by a scalar one */
+template <class S, bool NOISE, bool FAST, bool IN4, bool CLAMP, int ACT, int OT = 16, int OL = OT, bool KN = false>
 __global__ void __launch_bounds__(64)
 k_active(const crthip_params P, int n_fields, const unsigned char *__restrict__ images, size_t istride,
          signed char *__restrict__ dst, size_t fstride, const crthip_state *__restrict__ state,
@@ -451,6 +453,8 @@ k_active(const crthip_params P, int n_fields, const unsigned char *__restrict__ 
     const int f = live ? gid / rows : 0;
     const int y = live ? gid - f * rows : 0;
     const crthip_state st = state[f];
+    int noise = P.noise;
+    if constexpr (KN) noise = knob_blob_recs(P)[f].noise;
     const unsigned char *img = images + (size_t) f * istride;
     const int start = (y + P.yo) * S::HRES + P.xo;
     unsigned rn = 0;
@@ -488,7 +492,7 @@ k_active(const crthip_params P, int n_fields, const unsigned char *__restrict__ 
                     ire += ppu_level(p, phase + 3);
                     ire = (ire * P.white_point / 100) >> 12;
                     ire = (int) (signed char) ire;
-                    if (NOISE) { rn = lcg_step(rn); ire = noisy(ire, rn, P.noise); }
+                    if (NOISE) { rn = lcg_step(rn); ire = noisy(ire, rn, noise); }
                     else if (CLAMP) ire = clampi(ire, -127, 127);
                     pack |= (unsigned) (ire & 255) << (8 * k);
                     phase += 3;
@@ -517,7 +521,7 @@ k_active(const crthip_params P, int n_fields, const unsigned char *__restrict__ 
             for (int k = 0; k < 5; k++) { s_cc5[lane * CC5_STRIDE + 2 * k] = cI[k]; s_cc5[lane * CC5_STRIDE + 2 * k + 1] = cQ[k]; }
         }
         const int cy_ = P.iir_c[0], ci_ = P.iir_c[1], cq_ = P.iir_c[2];
-        const int white = P.white, ire_base = P.ire_base, noise = P.noise;
+        const int white = P.white, ire_base = P.ire_base;
         int hy = 0, hi = 0, hq = 0;
         const bool hipass = (P.flags & CRTHIP_F_HIPASS) != 0;
         int cph = 0;                                              /* x % CCS for the 5-sample system (wave-uniform) */
@@ -646,7 +650,7 @@ k_active(const crthip_params P, int n_fields, const unsigned char *__restrict__ 
                         const int nb = (int) ((rn >> 16) & 0xffu);
                         __builtin_amdgcn_sched_barrier(0);
                         const int pQ = __mul24(oq, ccQ);
-                        const int nz = mad24_vv(nb, noise256, neg_noise127_256);
+                        const int nz = KN ? mad24_vvv(nb, noise256, neg_noise127_256) : mad24_vv(nb, noise256, neg_noise127_256);
                         __builtin_amdgcn_sched_barrier(0);
                         const int miq = add_hiwords(pI, pQ);
                         ire = mad24_vv(oy + miq, white64, ire_base_65536);
@@ -681,7 +685,7 @@ k_active(const crthip_params P, int n_fields, const unsigned char *__restrict__ 
                         if (FAST) {
                             /* ((byte - 0x7f) * noise) >> 8 added to ire: the product scaled by 256 so that the
                              * shift becomes "take the high word" and rides on the add (|noise| < 2^15 on this path) */
-                            ire = add_hiwords(ire, mad24_vv(nb, noise256, neg_noise127_256));
+                            ire = add_hiwords(ire, KN ? mad24_vvv(nb, noise256, neg_noise127_256) : mad24_vv(nb, noise256, neg_noise127_256));
                         } else {
                             ire += (nb * noise + neg_noise127) >> 8;
                         }
@@ -712,7 +716,7 @@ k_active(const crthip_params P, int n_fields, const unsigned char *__restrict__ 
  *   C  modulate, scale, clamp, + noise, pack: fully parallel, a lane takes 4 consecutive samples (one dword store)
  * so a field is 30 waves and the serial chain per wave is 753 x 4 instructions.  Same arithmetic, exact 32-bit
  * multiplies throughout.  RGB-input systems only (the NES's table encoder is cheap as it is). */
-template <class S, bool NOISE, bool CLAMP>
+template <class S, bool NOISE, bool CLAMP, bool KN = false>
 __global__ void __launch_bounds__(64)
 k_active_row(const crthip_params P, int n_fields, const unsigned char *__restrict__ images, size_t istride,
              signed char *__restrict__ dst, size_t fstride, const crthip_state *__restrict__ state,
@@ -745,6 +749,7 @@ k_active_row(const crthip_params P, int n_fields, const unsigned char *__restric
     constexpr int CP = R / 4;
     const int c_rp = lane >> 4, c_j = lane & 15;
     int c_live[CP], c_start[CP], c_cI[CP][CCS], c_cQ[CP][CCS];
+    int c_noise[CP];                                     /* the noise gain of the pass's row: the batch's, or (KN) its field's */
     unsigned c_rn0[CP];
     unsigned long long c_dst[CP];
 #pragma unroll
@@ -756,6 +761,8 @@ k_active_row(const crthip_params P, int n_fields, const unsigned char *__restric
         c_start[ps] = (y + P.yo) * S::HRES + P.xo;                  /* flat sample index: the noise generator's position */
         c_dst[ps] = (unsigned long long) (dst + (size_t) f * fstride + (size_t) (shift + (y + P.yo) * pitch + P.xo));   /* k_active: pitch / shift / wrapn */
         c_rn0[ps] = (unsigned) st.rn;
+        c_noise[ps] = P.noise;
+        if constexpr (KN) c_noise[ps] = knob_blob_recs(P)[f].noise;
         const int crow = carrier_row<S>(y + P.yo, st.field, st.frame, st.aux);
 #pragma unroll
         for (int k = 0; k < CCS; k++) { c_cI[ps][k] = P.modI[crow][k]; c_cQ[ps][k] = P.modQ[crow][k]; }
@@ -770,7 +777,7 @@ k_active_row(const crthip_params P, int n_fields, const unsigned char *__restric
         const int sy = source_row<S>(P, y, field);
         a_src[r] = (unsigned long long) (images + (size_t) f * istride + (size_t) sy * w * in_bpp);
     }
-    const int white = P.white, ire_base = P.ire_base, noise = P.noise;
+    const int white = P.white, ire_base = P.ire_base;
 
     for (int t0 = 0; t0 < destw; t0 += TS) {
         /* ---- A: fetch + convert, lane = sample t0 + lane of every row ---- */
@@ -837,7 +844,7 @@ k_active_row(const crthip_params P, int n_fields, const unsigned char *__restric
                 const int mi = (hi * ccI) >> 4, mq = (hq * ccQ) >> 4;
                 int ire = ire_base + (((hy + mi + mq) * white) >> 10);
                 ire = clampi(ire, 0, 110);
-                if (NOISE) { rn = lcg_step(rn); ire = noisy(ire, rn, noise); }
+                if (NOISE) { rn = lcg_step(rn); ire = noisy(ire, rn, c_noise[ps]); }
                 else if (CLAMP) ire = clampi(ire, -127, 127);
                 smp[k] = ire;
             }
@@ -882,7 +889,7 @@ __global__ void k_nes_table(const crthip_params P, signed char *tab)
     tab[idx] = (signed char) ire;
 }
 
-template <class S, bool NOISE, bool CLAMP, int ACT>
+template <class S, bool NOISE, bool CLAMP, int ACT, bool KN = false>
 __global__ void __launch_bounds__(64)
 k_active_nes(const crthip_params P, int n_fields, const unsigned char *__restrict__ images, size_t istride,
              signed char *__restrict__ dst, size_t fstride, const crthip_state *__restrict__ state,
@@ -901,6 +908,8 @@ k_active_nes(const crthip_params P, int n_fields, const unsigned char *__restric
     const int f = live ? gid / rows : 0;
     const int y = live ? gid - f * rows : 0;
     const crthip_state st = state[f];
+    int noise = P.noise;
+    if constexpr (KN) noise = knob_blob_recs(P)[f].noise;
     const unsigned char *img = images + (size_t) f * istride;
     const int start = (y + P.yo) * S::HRES + P.xo;
     unsigned rn = 0;
@@ -933,7 +942,7 @@ k_active_nes(const crthip_params P, int n_fields, const unsigned char *__restric
                 const int p = (int) ((col & 1) ? dw >> 16 : dw & 0xffffu);
                 /* data[] is unsigned short (crt_nes.h:133): the reference's table walks only look at bits 0-8 */
                 int ire = tb[(p & 511) * 12 + ph];
-                if (NOISE) { rn = lcg_step(rn); ire = noisy(ire, rn, P.noise); }
+                if (NOISE) { rn = lcg_step(rn); ire = noisy(ire, rn, noise); }
                 else if (CLAMP) ire = clampi(ire, -127, 127);
                 smp[k] = ire;
                 ph += 3;
@@ -1005,7 +1014,7 @@ k_skeleton(const crthip_params P, signed char *__restrict__ skel, size_t fstride
  * end of a line simply continues in the next one) and each lane takes one run of up to 16 samples of it: 16 bytes
  * of the cached skeleton variant (k_skeleton), + noise (LCG state by the 16-step jump table and a 16-entry table
  * for the remainder). */
-template <class S, bool NOISE>
+template <class S, bool NOISE, bool KN = false>
 __global__ void __launch_bounds__(256)
 k_margin(const crthip_params P, int n_fields, signed char *__restrict__ dst, size_t fstride,
          const crthip_state *__restrict__ state, const uint2 *__restrict__ jump16, const uint2 *__restrict__ jump1,
@@ -1075,7 +1084,8 @@ k_margin(const crthip_params P, int n_fields, signed char *__restrict__ dst, siz
          * arithmetic as noisy() / lcg_step() */
         v2u lcg_add = { LCG_ADD, 0u };
         asm volatile("" : "+v"(lcg_add));
-        const int noise = P.noise;
+        int noise = P.noise;
+        if constexpr (KN) noise = knob_blob_recs(P)[f].noise;
 #pragma unroll
         for (int k = 0; k < 16; k++) {
             rn = lcg_step_mad64(rn, lcg_add);
@@ -1116,7 +1126,7 @@ k_margin(const crthip_params P, int n_fields, signed char *__restrict__ dst, siz
  * a0 = wrap for a line whose predecessor carries an active row (the row's last `wrap` samples run into this line: k_active's), else 0.
  * A chunk that lies inside the first PADC columns of line n >= 1 is stored a second time behind line n - 1 (the copy that makes
  * windows over a line end contiguous); chunks that only partly do are not -- `padv` (crt_fused_layout) is what that guarantees. */
-template <class S, bool NOISE>
+template <class S, bool NOISE, bool KN = false>
 __global__ void __launch_bounds__(256)
 k_margin_pad(const crthip_params P, int n_fields, signed char *__restrict__ dst, size_t fstride, int shift,
              const crthip_state *__restrict__ state, const uint2 *__restrict__ jump16, const uint2 *__restrict__ jump1,
@@ -1166,7 +1176,8 @@ k_margin_pad(const crthip_params P, int n_fields, signed char *__restrict__ dst,
         int vals[16];
         v2u lcg_add = { LCG_ADD, 0u };
         asm volatile("" : "+v"(lcg_add));
-        const int noise = P.noise;
+        int noise = P.noise;
+        if constexpr (KN) noise = knob_blob_recs(P)[f].noise;
 #pragma unroll
         for (int i = 0; i < 16; i++) {
             rn = lcg_step_mad64(rn, lcg_add);
@@ -1236,6 +1247,12 @@ static void launch_active(crthip_ctx *c, const crthip_params *p, int n, const vo
         if (p->w >= 8) {
             /* the sample table depends on the black / white point only: rebuilt when those change, always on the
              * context's main stream (crt_run_encoder_prepare), never concurrently with a reader */
+            if constexpr (FULL) {
+                if (p->noise != 0 && c->knob_recs) {
+                    hipLaunchKernelGGL((k_active_nes<S, true, true, 16, true>), grid, block, 0, c->stream, *p, n, img, istride, dst, lay.fstride, d_state, c->d_jump16, c->d_nes_tab, lay.pitch, lay.shift, wrapn);
+                    return;
+                }
+            }
             if (FULL && p->noise != 0)
                 hipLaunchKernelGGL((k_active_nes<S, true, FULL, 16>), grid, block, 0, c->stream, *p, n, img, istride, dst, lay.fstride, d_state, c->d_jump16, c->d_nes_tab, lay.pitch, lay.shift, wrapn);
             else
@@ -1244,10 +1261,17 @@ static void launch_active(crthip_ctx *c, const crthip_params *p, int n, const vo
         }
     }
     const bool noise = FULL && p->noise != 0;
+    const bool kn = noise && c->knob_recs;                       /* per-field noise: the KN instantiations (fused path only) */
     if constexpr (!S::IS_NES) {
         /* kernel shape (crthip_set_shape): small batches take the scanline-parallel encoder */
         if (c->shape == 2 || (c->shape == 0 && n <= ROWS_SHAPE_MAX_FIELDS_ENC)) {
             const dim3 rgrid((total + 7) / 8);
+            if constexpr (FULL) {
+                if (kn) {
+                    hipLaunchKernelGGL((k_active_row<S, true, true, true>), rgrid, block, 0, c->stream, *p, n, img, istride, dst, lay.fstride, d_state, c->d_jump16, c->d_jump1, lay.pitch, lay.shift, wrapn);
+                    return;
+                }
+            }
             if (noise) hipLaunchKernelGGL((k_active_row<S, true, FULL>), rgrid, block, 0, c->stream, *p, n, img, istride, dst, lay.fstride, d_state, c->d_jump16, c->d_jump1, lay.pitch, lay.shift, wrapn);
             else hipLaunchKernelGGL((k_active_row<S, false, FULL>), rgrid, block, 0, c->stream, *p, n, img, istride, dst, lay.fstride, d_state, c->d_jump16, c->d_jump1, lay.pitch, lay.shift, wrapn);
             return;
@@ -1280,17 +1304,24 @@ static void launch_active(crthip_ctx *c, const crthip_params *p, int n, const vo
 #ifndef CRTHIP_ENC_OL64
 #define CRTHIP_ENC_OL64 32
 #endif
-#define CRTHIP_LAUNCH_ACTIVE_BIG(NZ) \
-    do { if (wide_in) hipLaunchKernelGGL((k_active<S, NZ, true, true, true, 32, 64, CRTHIP_ENC_OL64>), ogrid, block, 0, c->stream, *p, n, img, istride, dst, lay.fstride, d_state, c->d_jump16, bo.K, bo.per, lay.pitch, lay.shift, wrapn); \
-         else hipLaunchKernelGGL((k_active<S, NZ, true, true, true, 16, 32, CRTHIP_ENC_OL32>), ogrid, block, 0, c->stream, *p, n, img, istride, dst, lay.fstride, d_state, c->d_jump16, bo.K, bo.per, lay.pitch, lay.shift, wrapn); } while (0)
-            if (noise) CRTHIP_LAUNCH_ACTIVE_BIG(true); else CRTHIP_LAUNCH_ACTIVE_BIG(false);
+#define CRTHIP_LAUNCH_ACTIVE_BIG(NZ, ...) \
+    do { if (wide_in) hipLaunchKernelGGL((k_active<S, NZ, true, true, true, 32, 64, CRTHIP_ENC_OL64 __VA_ARGS__>), ogrid, block, 0, c->stream, *p, n, img, istride, dst, lay.fstride, d_state, c->d_jump16, bo.K, bo.per, lay.pitch, lay.shift, wrapn); \
+         else hipLaunchKernelGGL((k_active<S, NZ, true, true, true, 16, 32, CRTHIP_ENC_OL32 __VA_ARGS__>), ogrid, block, 0, c->stream, *p, n, img, istride, dst, lay.fstride, d_state, c->d_jump16, bo.K, bo.per, lay.pitch, lay.shift, wrapn); } while (0)
+            if (kn) CRTHIP_LAUNCH_ACTIVE_BIG(true, , true);
+            else if (noise) CRTHIP_LAUNCH_ACTIVE_BIG(true); else CRTHIP_LAUNCH_ACTIVE_BIG(false);
 #undef CRTHIP_LAUNCH_ACTIVE_BIG
             return;
         }
     }
-#define CRTHIP_LAUNCH_ACTIVE(NZ, I4) \
-    do { if (wide_in) hipLaunchKernelGGL((k_active<S, NZ, FAST, I4, FULL, 32>), ogrid, block, 0, c->stream, *p, n, img, istride, dst, lay.fstride, d_state, c->d_jump16, bo.K, bo.per, lay.pitch, lay.shift, wrapn); \
-         else hipLaunchKernelGGL((k_active<S, NZ, FAST, I4, FULL, 16>), ogrid, block, 0, c->stream, *p, n, img, istride, dst, lay.fstride, d_state, c->d_jump16, bo.K, bo.per, lay.pitch, lay.shift, wrapn); } while (0)
+#define CRTHIP_LAUNCH_ACTIVE(NZ, I4, ...) \
+    do { if (wide_in) hipLaunchKernelGGL((k_active<S, NZ, FAST, I4, FULL, 32 __VA_ARGS__>), ogrid, block, 0, c->stream, *p, n, img, istride, dst, lay.fstride, d_state, c->d_jump16, bo.K, bo.per, lay.pitch, lay.shift, wrapn); \
+         else hipLaunchKernelGGL((k_active<S, NZ, FAST, I4, FULL, 16 __VA_ARGS__>), ogrid, block, 0, c->stream, *p, n, img, istride, dst, lay.fstride, d_state, c->d_jump16, bo.K, bo.per, lay.pitch, lay.shift, wrapn); } while (0)
+    if constexpr (FULL) {
+        if (kn) {                                                /* (the default tiles spelt out: KN is the last parameter) */
+            if (in4) CRTHIP_LAUNCH_ACTIVE(true, true, , 16, 16, true); else CRTHIP_LAUNCH_ACTIVE(true, false, , 16, 16, true);
+            return;
+        }
+    }
     if (noise) { if (in4) CRTHIP_LAUNCH_ACTIVE(true, true); else CRTHIP_LAUNCH_ACTIVE(true, false); }
     else       { if (in4) CRTHIP_LAUNCH_ACTIVE(false, true); else CRTHIP_LAUNCH_ACTIVE(false, false); }
 #undef CRTHIP_LAUNCH_ACTIVE
@@ -1309,7 +1340,10 @@ static void launch_margins(crthip_ctx *c, const crthip_params *p, int n, signed 
     const int per_field = head + (p->desth - 1) * gap + tail;
     const unsigned gap_magic = gap > 0 ? (unsigned) ((0x100000000ull + (unsigned) gap - 1) / (unsigned) gap) : 0u;
     const dim3 grid((per_field + 255) / 256, n < 65535 ? n : 65535);          /* (fields beyond the grid's y limit: the kernel loops) */
-    if (p->noise != 0)
+    if (p->noise != 0 && c->knob_recs)
+        hipLaunchKernelGGL((k_margin<S, true, true>), grid, dim3(256), 0, c->stream,
+                           *p, n, dst, c->fstride, d_state, c->d_jump16, c->d_jump1, c->d_skel, head, gap, tail, gap_magic);
+    else if (p->noise != 0)
         hipLaunchKernelGGL((k_margin<S, true>), grid, dim3(256), 0, c->stream,
                            *p, n, dst, c->fstride, d_state, c->d_jump16, c->d_jump1, c->d_skel, head, gap, tail, gap_magic);
     else
@@ -1331,7 +1365,10 @@ static void launch_margins_padded(crthip_ctx *c, const crthip_params *p, int n, 
     const unsigned act_magic = act_per > 1 ? (unsigned) ((0x100000000ull + (unsigned) act_per - 1) / (unsigned) act_per) : 0u;
     const int per_field = p->yo * CF + p->desth * act_per + (S::VRES - p->yo - p->desth) * CF;
     const dim3 grid((per_field + 255) / 256, n < 65535 ? n : 65535);
-    if (p->noise != 0)
+    if (p->noise != 0 && c->knob_recs)
+        hipLaunchKernelGGL((k_margin_pad<S, true, true>), grid, dim3(256), 0, c->stream, *p, n, dst, lay.fstride, lay.shift, d_state,
+                           c->d_jump16, c->d_jump1, c->d_skel, c->fstride, cl, cr, act_magic, lay.wrap);
+    else if (p->noise != 0)
         hipLaunchKernelGGL((k_margin_pad<S, true>), grid, dim3(256), 0, c->stream, *p, n, dst, lay.fstride, lay.shift, d_state,
                            c->d_jump16, c->d_jump1, c->d_skel, c->fstride, cl, cr, act_magic, lay.wrap);
     else

@@ -914,6 +914,13 @@ static int fieldpass_chunk(crthip_ctx *c, const crthip_params *p, int enc, int f
     crthip_line *ln = c->d_lines + (size_t) first * c->sd.lines;
     int rc = CRTHIP_OK;
     bool preset = false;
+    /* per-field knobs: the blob of this chunk's launches points at the record of ITS first field (crt_dev.h, knob_blob_set) */
+    crthip_params pk;
+    if (c->knob_recs) {
+        pk = *p;
+        knob_blob_set(&pk, c->knob_recs + first);
+        p = &pk;
+    }
     if (part & 1) {
         const bool vhs_rand = c->system == CRTHIP_SYSTEM_NTSCVHS && !(p->flags & CRTHIP_F_VHS_LCG_NOISE);
         if (vhs_rand || (p->flags & CRTHIP_F_NO_VSYNC)) {
@@ -956,7 +963,8 @@ static int fieldpass_chunk(crthip_ctx *c, const crthip_params *p, int enc, int f
         if (rc) return rc;
     }
     if ((part & 4) && p->out_bpp != 0) {
-        const crthip_params q = enc == 0 ? with_signal_envelope(p) : *p;
+        crthip_params q = enc == 0 && !c->knob_recs ? with_signal_envelope(p) : *p;
+        if (enc == 0 && c->knob_recs) q.loskip_wave_max = c->knob_loskip;      /* the envelope at the batch's widest noise (crthip_knobs_prepare) */
         rc = crt_run_sync(c, &q, n, inp, st, ln, 1, preset ? 1 : 0, &lay);
         if (rc) return rc;
     }
@@ -969,8 +977,9 @@ static int fieldpass_chunk(crthip_ctx *c, const crthip_params *p, int enc, int f
     return rc;
 }
 
-int crthip_fieldpass(crthip_ctx *c, const crthip_params *p, int n, const void *d_images, size_t istride,
-                     void *d_out, size_t ostride, crthip_state *d_state)
+/* crthip_fieldpass, and crthip_fieldpass_knobs when c->knob_recs is set (p is then the library's copy carrying the batch's bounds) */
+static int fieldpass_body(crthip_ctx *c, const crthip_params *p, int n, const void *d_images, size_t istride,
+                          void *d_out, size_t ostride, crthip_state *d_state)
 {
     int rc = check_params(c, p, n);
     if (rc) return rc;
@@ -1046,6 +1055,38 @@ int crthip_fieldpass(crthip_ctx *c, const crthip_params *p, int n, const void *d
     c->last_lay = lay;
     c->last_n = n;
     return CRTHIP_OK;
+}
+
+int crthip_fieldpass(crthip_ctx *c, const crthip_params *p, int n, const void *d_images, size_t istride,
+                     void *d_out, size_t ostride, crthip_state *d_state)
+{
+    if (c) c->knob_recs = nullptr;
+    return fieldpass_body(c, p, n, d_images, istride, d_out, ostride, d_state);
+}
+
+int crthip_fieldpass_knobs(crthip_ctx *c, const crthip_params *p, int n, const void *d_images, size_t istride,
+                           void *d_out, size_t ostride, crthip_state *d_state, const crthip_knob_rec *d_recs, const crthip_knobs_env *env)
+{
+    int rc = check_params(c, p, n);
+    if (rc) return rc;
+    if (!d_recs || !env) return CRTHIP_E_ARG;
+    if (env->magic != CRTHIP_KNOBS_MAGIC) return set_err(c, CRTHIP_E_ARG, "knobs: env does not come from crthip_knobs_prepare", hipSuccess);
+    if (env->n != n) return set_err(c, CRTHIP_E_ARG, "knobs: env was prepared for another number of fields", hipSuccess);
+    if ((p->flags & CRTHIP_PHOSPHOR_MASK) == CRTHIP_PHOSPHOR_MASK)
+        return set_err(c, CRTHIP_E_ARG, "phosphor fade and clear at once (crt_main.c:459-463: one or the other)", hipSuccess);
+    if (c->sd.cc_samples == 5)
+        return set_err(c, CRTHIP_E_ARG, "knobs: the 5-sample decoder (PV-1000) takes monitor hue and saturation from the uniform parameters", hipSuccess);
+    if (env->noise_max < 0 || env->sat_abs_max < 0) return set_err(c, CRTHIP_E_ARG, "knobs: env bounds", hipSuccess);
+    /* the blob the launch code decides by: the batch's bounds where it reads the uniform values (noise != 0, the encoder's 24-bit
+     * envelope); mon_hue / huesn / huecs / bloom_max_e are read by the KN kernels alone, from the records */
+    crthip_params q = *p;
+    q.noise = env->noise_max;
+    q.saturation = env->sat_abs_max;
+    c->knob_loskip = env->loskip_wave_max < LOSKIP_WAVE_MAX ? LOSKIP_WAVE_MAX : env->loskip_wave_max > T0_WAVE_MAX ? T0_WAVE_MAX : env->loskip_wave_max;
+    c->knob_recs = d_recs;
+    rc = fieldpass_body(c, &q, n, d_images, istride, d_out, ostride, d_state);
+    c->knob_recs = nullptr;
+    return rc;
 }
 
 /* ---- stills ---------------------------------------------------------------------------------------------------------------- */

@@ -4,7 +4,8 @@
 /* ------------------------------------------------------------------------- */
 /* D1: channel noise (elementwise, 16 samples per lane)                        */
 /* ------------------------------------------------------------------------- */
-template <class S>
+/* KN (all three noise kernels): the gain of the lane's / wave's field from its crthip_knob_rec (crt_dev.h) */
+template <class S, bool KN = false>
 __global__ void __launch_bounds__(256)
 k_noise(const crthip_params P, int n_fields, const signed char *__restrict__ analog,
         signed char *__restrict__ inp, size_t fstride, const crthip_state *__restrict__ state,
@@ -26,7 +27,8 @@ k_noise(const crthip_params P, int n_fields, const signed char *__restrict__ ana
      * noisy(); v_mul_lo_u32 runs at a quarter of its rate) */
     v2u lcg_add = { LCG_ADD, 0u };
     asm volatile("" : "+v"(lcg_add));
-    const int noise = P.noise;
+    int noise = P.noise;
+    if constexpr (KN) noise = knob_blob_recs(P)[f].noise;
 #pragma unroll
     for (int d = 0; d < 4; d++) {
         int v[4];
@@ -198,7 +200,7 @@ __device__ __forceinline__ void vhs_jump_mfma(const unsigned char *s_zd, const v
 /* Parallel region.  A wave's 64 chunks (VHS_CHUNK = 124 samples each) are (mostly) one contiguous 7936-byte run of the field: it
  * is moved through an LDS tile of 64 x 31 dwords with coalesced requests (lane-per-chunk byte accesses cost 12x the algorithmic
  * HBM write traffic); a chunk's 31 dwords are an odd stride already: the lane-per-chunk accesses are conflict-free. */
-template <class S, bool MFMA>
+template <class S, bool MFMA, bool KN = false>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4)))
 k_vhs_noise(const crthip_params P, int n_fields, const signed char *__restrict__ analog,
             signed char *__restrict__ inp, size_t fstride,
@@ -310,7 +312,8 @@ k_vhs_noise(const crthip_params P, int n_fields, const signed char *__restrict__
             for (int j = 0; j < 31; j++) w[j] += cm[m] * z[m + j];
         }
     }
-    const int noise = P.noise;
+    int noise = P.noise;
+    if constexpr (KN) noise = knob_blob_recs(P)[f].noise;
     __syncthreads();
     /* 2 calls per sample; ring index = call % 31 is static */
     unsigned *mine = s_t + lane * DWS;
@@ -368,7 +371,7 @@ k_vhs_noise(const crthip_params P, int n_fields, const signed char *__restrict__
  * streams said; at 168 one wave of k_vhs_noise fits next to them: 0.845 -> 0.785 ms for the pair, profiles/r04_experiments.txt) */
 #define VHS_COS_TAB 24                                         /* >= (HRES * 17) / HRES + 2 distinct values of (i * line) / HRES per segment */
 #define VHS_DIV_MAGIC(h) ((unsigned long long) ((((1ull << 40) + (h) - 1) / (h))))
-template <class S, bool MFMA>
+template <class S, bool MFMA, bool KN = false>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3)))
 k_vhs_tail(const crthip_params P, int n_fields, const signed char *__restrict__ analog,
            signed char *__restrict__ inp, size_t fstride, crthip_state *__restrict__ state,
@@ -393,7 +396,8 @@ k_vhs_tail(const crthip_params P, int n_fields, const signed char *__restrict__ 
     const unsigned *h = hist + (size_t) f * 32;
     const signed char *src = analog + (size_t) f * fstride;
     signed char *dst = inp + (size_t) f * fstride;
-    const int noise = P.noise;
+    int noise = P.noise;
+    if constexpr (KN) noise = knob_blob_recs(P)[f].noise;
 
     /* the field's base sequence -> the history in front of call 1 + 2*T0 (lane j computes element j) */
     int vhs_line;
@@ -749,11 +753,20 @@ int crt_run_noise(crthip_ctx *c, const crthip_params *p, int n, const signed cha
                 const unsigned *tail_row = c->d_vhs_rows + (size_t) c->vhs_chunks * 31, *blk_rows = c->d_vhs_rows + (size_t) (c->vhs_chunks + 1) * 31;
                 const signed char *dig_blocks = c->d_vhs_dig + (size_t) c->vhs_chunks * VHS_DIG_ROW;
                 const bool mfma = c->vhs_mfma != 0;            /* the 31 x 31 jumps on the matrix cores (CRTHIP_VHS_MFMA=0: on the vector unit) */
+                const bool kn = c->knob_recs != nullptr;       /* per-field noise (crthip_fieldpass_knobs) */
 #define CRT_LAUNCH_TAIL(HOUT) do { \
-                if (mfma) hipLaunchKernelGGL((k_vhs_tail<S, true>), dim3(n), dim3(64), 0, c->stream, *p, n, d_analog, d_inp, c->fstride, d_state, c->d_vhs_hist, HOUT, tail_row, blk_rows, dig_blocks); \
+                if (kn && mfma) hipLaunchKernelGGL((k_vhs_tail<S, true, true>), dim3(n), dim3(64), 0, c->stream, *p, n, d_analog, d_inp, c->fstride, d_state, c->d_vhs_hist, HOUT, tail_row, blk_rows, dig_blocks); \
+                else if (kn) hipLaunchKernelGGL((k_vhs_tail<S, false, true>), dim3(n), dim3(64), 0, c->stream, *p, n, d_analog, d_inp, c->fstride, d_state, c->d_vhs_hist, HOUT, tail_row, blk_rows, dig_blocks); \
+                else if (mfma) hipLaunchKernelGGL((k_vhs_tail<S, true>), dim3(n), dim3(64), 0, c->stream, *p, n, d_analog, d_inp, c->fstride, d_state, c->d_vhs_hist, HOUT, tail_row, blk_rows, dig_blocks); \
                 else hipLaunchKernelGGL((k_vhs_tail<S, false>), dim3(n), dim3(64), 0, c->stream, *p, n, d_analog, d_inp, c->fstride, d_state, c->d_vhs_hist, HOUT, tail_row, blk_rows, dig_blocks); } while (0)
                 if (side) CRT_LAUNCH_TAIL(c->d_vhs_next);
-                if (mfma)
+                if (kn && mfma)
+                    hipLaunchKernelGGL((k_vhs_noise<S, true, true>), dim3((n * c->vhs_chunks + 63) / 64), dim3(64), 0, ns,
+                                       *p, n, d_analog, d_inp, c->fstride, c->d_vhs_hist, c->d_vhs_rows, c->vhs_chunks, c->d_vhs_dig);
+                else if (kn)
+                    hipLaunchKernelGGL((k_vhs_noise<S, false, true>), dim3((n * c->vhs_chunks + 63) / 64), dim3(64), 0, ns,
+                                       *p, n, d_analog, d_inp, c->fstride, c->d_vhs_hist, c->d_vhs_rows, c->vhs_chunks, c->d_vhs_dig);
+                else if (mfma)
                     hipLaunchKernelGGL((k_vhs_noise<S, true>), dim3((n * c->vhs_chunks + 63) / 64), dim3(64), 0, ns,
                                        *p, n, d_analog, d_inp, c->fstride, c->d_vhs_hist, c->d_vhs_rows, c->vhs_chunks, c->d_vhs_dig);
                 else
@@ -776,6 +789,10 @@ int crt_run_noise(crthip_ctx *c, const crthip_params *p, int n, const signed cha
         constexpr int CHUNKS = (S::INPUT_SIZE + 15) / 16;
         {
             ProfScope ps(c, CRTHIP_K_NOISE);
+            if (c->knob_recs)
+                hipLaunchKernelGGL((k_noise<S, true>), dim3((n * CHUNKS + 255) / 256), dim3(256), 0, c->stream,
+                                   *p, n, d_analog, d_inp, c->fstride, d_state, c->d_jump16);
+            else
             hipLaunchKernelGGL((k_noise<S>), dim3((n * CHUNKS + 255) / 256), dim3(256), 0, c->stream,
                                *p, n, d_analog, d_inp, c->fstride, d_state, c->d_jump16);
         }

@@ -685,6 +685,71 @@ crt_setup_loskip_bound(int lo, int hi)
 }
 
 /* ------------------------------------------------------------------------- */
+/* per-field knobs (crthip_fieldpass_knobs)                                    */
+/* ------------------------------------------------------------------------- */
+static int
+abs_sat(int v)
+{
+    if (v >= 0) {
+        return v;
+    }
+    return v < -0x7fffffff ? 0x7fffffff : -v;
+}
+
+/*
+ * The per-field records and the batch-wide bounds of n knob triples: field by field what crthip_params_finalize derives from
+ * mon_hue (huesn / huecs) and noise (bloom_max_e), its refusals included; the bounds are what the launch code otherwise reads
+ * from the uniform noise and saturation.  The signal range grows with the noise on either side of zero, so the no-low-cascade
+ * bound of the batch is the smaller of the bounds at the smallest and the largest noise.
+ */
+int
+crthip_knobs_prepare(const crthip_params *p, int n, const crthip_knobs *knobs, crthip_knob_rec *recs, crthip_knobs_env *env)
+{
+    struct crt_sysdef d;
+    crthip_params q;
+    int k, sn, cs, lo, hi, bound, b2;
+    int noise_lo, noise_hi, noise_abs = 0, sat_abs = 0;
+
+    if (p == 0 || knobs == 0 || recs == 0 || env == 0 || n <= 0 || p->finalized != CRTHIP_PARAMS_MAGIC ||
+        crt_sysdef_get(&d, p->system, p->chroma_pattern) != CRTHIP_OK) {
+        return CRTHIP_E_ARG;
+    }
+    memset(env, 0, sizeof(*env));
+    noise_lo = noise_hi = knobs[0].noise;
+    for (k = 0; k < n; k++) {
+        const int noise = knobs[k].noise;
+        const int max_e = (128 + (noise / 2)) * d.av_len;           /* crt_core.c:400 */
+        if (p->bloom && (max_e <= 0 || noise < 0)) {
+            return CRTHIP_E_ARG;                                    /* as crthip_params_finalize */
+        }
+        memset(&recs[k], 0, sizeof(recs[k]));
+        crt_setup_sincos14(&sn, &cs, ((knobs[k].mon_hue % 360) + 33) * 8192 / 180);      /* crt_core.c:318-320 */
+        recs[k].noise = noise;
+        recs[k].huesn = sn >> 11;
+        recs[k].huecs = cs >> 11;
+        recs[k].saturation = knobs[k].saturation;
+        recs[k].bloom_max_e = max_e;
+        if (noise < noise_lo) noise_lo = noise;
+        if (noise > noise_hi) noise_hi = noise;
+        if (abs_sat(noise) > noise_abs) noise_abs = abs_sat(noise);
+        if (abs_sat(knobs[k].saturation) > sat_abs) sat_abs = abs_sat(knobs[k].saturation);
+    }
+    q = *p;
+    q.noise = noise_lo;
+    crt_setup_signal_range(&q, &lo, &hi);
+    bound = crt_setup_loskip_bound(lo, hi);
+    q.noise = noise_hi;
+    crt_setup_signal_range(&q, &lo, &hi);
+    b2 = crt_setup_loskip_bound(lo, hi);
+    env->magic = CRTHIP_KNOBS_MAGIC;
+    env->n = n;
+    env->noise_max = noise_abs;
+    env->sat_abs_max = sat_abs;
+    env->loskip_wave_max = b2 < bound ? b2 : bound;
+    return CRTHIP_OK;
+}
+
+/* ------------------------------------------------------------------------- */
 /* VHS: the C library's rand() (crt_core.c:344,349-351; crt_ntscvhs.c:206)    */
 /* ------------------------------------------------------------------------- */
 /*

@@ -56,6 +56,7 @@ void crt_setup_vhs_power(unsigned long k, unsigned c[31]);
 void crt_setup_vhs_power_table(unsigned long first, unsigned long step, int count, unsigned *rows);
 
 #define CRTHIP_PARAMS_MAGIC 0x43525431            /* "CRT1" */
+#define CRTHIP_KNOBS_MAGIC  0x43524b31            /* "CRK1": crthip_knobs_env of crthip_knobs_prepare */
 
 /* CRTHIP_F_PHOSPHOR_FADE / _CLEAR (crt_hip.h): fade^CRTHIP_PHOSPHOR_DEPTH(c) == 0 for every byte c, fade^(DEPTH-1)(255) != 0 */
 #define CRTHIP_PHOSPHOR_MASK  (CRTHIP_F_PHOSPHOR_FADE | CRTHIP_F_PHOSPHOR_CLEAR)

@@ -166,7 +166,8 @@ __device__ __forceinline__ int burst_step(int acc, int s)
  * `padv` valid bytes of the next line's head behind each.  Every window below is then addressed through sig_phys (line and column
  * of its first byte; contiguous from there), the line table's pos becomes an offset in the padded field, and the few lines whose
  * decoder window would run past the valid copy (hsync far from lock) get that window copied into a scratch row behind the field. */
-template <class S, int FPB, bool PAD>
+/* KN: monitor hue and saturation (and, k_bloom, the noise term of max_e) of the wave's field from its crthip_knob_rec (crt_dev.h) */
+template <class S, int FPB, bool PAD, bool KN = false>
 __global__ void __launch_bounds__(64 * FPB, 4)
 k_hsync_wave(const crthip_params P, int n_fields, const signed char *__restrict__ inp, size_t fstride,
              crthip_state *__restrict__ state, crthip_line *__restrict__ lines, uint2 whole_field, int advance_rn,
@@ -205,6 +206,11 @@ k_hsync_wave(const crthip_params P, int n_fields, const signed char *__restrict_
     /* offset of flat sample index a (>= 0) from `in` */
     auto phys = [&](int a) { return PAD ? sig_phys<S>(a) : a; };
     crthip_state *st = state + f;
+    int huesn = P.huesn, huecs = P.huecs, saturation = P.saturation;
+    if constexpr (KN) {
+        const crthip_knob_rec *kr = knob_blob_recs(P) + f;
+        huesn = kr->huesn; huecs = kr->huecs; saturation = kr->saturation;
+    }
     int hsync = __builtin_amdgcn_readfirstlane(st->hsync);
     /* D2: the vertical sync search of this field, by the field's own wave (one launch and one trip through memory less
      * than a kernel of its own; what a single field-pass costs is mostly this chain's latency) */
@@ -484,8 +490,8 @@ k_hsync_wave(const crthip_params P, int n_fields, const signed char *__restrict_
                     if constexpr (CCS == 4) {                              /* :471-472 */
                         dci = ac[(pa + 1) & 3] - ac[(pa + 3) & 3];
                         dcq = ac[(pa + 2) & 3] - ac[(pa + 0) & 3];
-                        lp.wave0 = ((dci * P.huecs - dcq * P.huesn) >> 4) * P.saturation;
-                        lp.wave1 = ((dcq * P.huecs + dci * P.huesn) >> 4) * P.saturation;
+                        lp.wave0 = ((dci * huecs - dcq * huesn) >> 4) * saturation;
+                        lp.wave1 = ((dcq * huecs + dci * huesn) >> 4) * saturation;
                     } else {                                               /* :480-494 */
                         const int peak_a = pa + CCS / 4, peak_b = pa;
                         const int dci_a = ac[peak_a % CCS];
@@ -511,7 +517,7 @@ k_hsync_wave(const crthip_params P, int n_fields, const signed char *__restrict_
                             rank++;
                     }
                     nrows |= (rank & CRTHIP_LINE_RANK_MASK) << CRTHIP_LINE_RANK_SHIFT;
-                    nrows |= line_tier_flags<CCS>(lp.wave0, lp.wave1, P.saturation, P.loskip_wave_max, reads_tail);
+                    nrows |= line_tier_flags<CCS>(lp.wave0, lp.wave1, saturation, P.loskip_wave_max, reads_tail);
                     lp.nrows = nrows;
                 }
                 v4i a, b;
@@ -565,7 +571,7 @@ k_hsync_wave(const crthip_params P, int n_fields, const signed char *__restrict_
  *   2. the input term of :518 does not depend on the chain: one lane per line computes it (the division by max_e);
  *   3. the 240-step chain is now multiply, divide by 128, add: walked by wave 0 on the scalar unit;
  *   4. one lane per line turns prev_e into line_w, dx (the division by outw) and scanL, and patches the line table. */
-template <class S>
+template <class S, bool KN = false>
 __global__ void __launch_bounds__(256)
 k_bloom(const crthip_params P, int n_fields, const signed char *__restrict__ inp, size_t fstride,
         crthip_line *__restrict__ lines)
@@ -619,7 +625,8 @@ k_bloom(const crthip_params P, int n_fields, const signed char *__restrict__ inp
             if (lane == 0 && l0 + 4 * u < S::LINES) s_sum[l0 + 4 * u] = sum[u];
     }
     __syncthreads();
-    const int max_e = P.bloom_max_e;                                      /* :400 */
+    int max_e = P.bloom_max_e;                                            /* :400 */
+    if constexpr (KN) max_e = knob_blob_recs(P)[f].bloom_max_e;
     if (t < S::LINES && s_nrows[t] != 0) s_sum[t] = (((max_e >> 1) - s_sum[t]) << 10) / max_e;
     __syncthreads();
     if (t < 64) {
@@ -686,15 +693,22 @@ int crt_run_sync(crthip_ctx *c, const crthip_params *p, int n, const signed char
         const size_t fstride = lay ? lay->fstride : c->fstride;
         const int shift = pad ? lay->shift : 0, padv = pad ? lay->padv : 0;
         const bool fpb4 = FPB4_OK && c->sync_kernel != 2 && (n >= SYNC_FPB4_MIN_FIELDS || c->sync_kernel == 3);
-#define CRTHIP_LAUNCH_SYNC(FPB, PADV) \
+#define CRTHIP_LAUNCH_SYNC(FPB, PADV) do { \
+    if (c->knob_recs) \
+    hipLaunchKernelGGL((k_hsync_wave<S, FPB, PADV, true>), dim3((n + FPB - 1) / FPB), dim3(64 * FPB), 0, c->stream, *p, n, d_inp, fstride, d_state, d_lines, \
+                       c->whole_field, advance_rn, preset_ccf, shift, padv, pad ? const_cast<signed char *>(d_inp) : nullptr); \
+    else \
     hipLaunchKernelGGL((k_hsync_wave<S, FPB, PADV>), dim3((n + FPB - 1) / FPB), dim3(64 * FPB), 0, c->stream, *p, n, d_inp, fstride, d_state, d_lines, \
-                       c->whole_field, advance_rn, preset_ccf, shift, padv, pad ? const_cast<signed char *>(d_inp) : nullptr)   /* (padded: the library's own workspace) */
+                       c->whole_field, advance_rn, preset_ccf, shift, padv, pad ? const_cast<signed char *>(d_inp) : nullptr);   /* (padded: the library's own workspace) */ \
+    } while (0)
         if constexpr (FPB4_OK) {
             if (fpb4) { if (pad) CRTHIP_LAUNCH_SYNC(4, true); else CRTHIP_LAUNCH_SYNC(4, false); }
         }
         if (!fpb4) { if (pad) CRTHIP_LAUNCH_SYNC(1, true); else CRTHIP_LAUNCH_SYNC(1, false); }
 #undef CRTHIP_LAUNCH_SYNC
-        if (p->bloom)
+        if (p->bloom && c->knob_recs)
+            hipLaunchKernelGGL((k_bloom<S, true>), dim3(n), dim3(256), 0, c->stream, *p, n, d_inp, fstride, d_lines);
+        else if (p->bloom)
             hipLaunchKernelGGL((k_bloom<S>), dim3(n), dim3(256), 0, c->stream, *p, n, d_inp, fstride, d_lines);
         return CRTHIP_OK;
     });
