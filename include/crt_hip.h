@@ -352,6 +352,38 @@ int  crthip_sequence_sets(crthip_ctx *ctx, const crthip_params *p,
                           crthip_state *d_state, int *passes);
 
 /*
+ * SEQUENCE mode WITH PER-FIELD KNOBS: one running television set whose channel noise, monitor hue and saturation change from field to
+ * field -- the reference's interactive driver with its user at the knobs (crt_main.c:351-391 between two displaycb calls): a tape
+ * whose noise rises over a clip, a hue drift, a saturation fade-in, a recorded session of the live viewer.
+ * crthip_sequence_knobs: byte for byte and state for state the serial loop on ONE struct CRT -- for field k in order: noise, mon_hue
+ * and saturation <- field k's knobs; crt_modulate; crt_demodulate(noise_k); image k = the buffer after field k, d_state[k] = the state
+ * after field k -- i.e. what crthip_sequence would give if those three members of crthip_params could change per field.  (A field
+ * with noise 0 inside a noisy video runs with gain 0 and advances rn like every other: crt_core.c:358-366.)
+ * crthip_sequence_sets_knobs == crthip_sequence_knobs called once per set on the set's slices of d_images, d_out, d_state AND d_recs
+ * (record k belongs to field k of the batch; ONE crthip_knobs_prepare over all n = set_first[n_sets] fields gives the env).
+ *   d_recs / env : exactly as for crthip_fieldpass_knobs -- crthip_knobs_prepare over the n fields of the call, the records uploaded by
+ *   the caller (DEVICE memory; read by the kernels on every pass of the sync fixed point), env on the host.
+ * Whatever the uniform entry point accepts is accepted with the same meaning (blend, the phosphor flags, FIR, bloom -- max_e per field --,
+ * both kernel shapes, every 4-sample system, the rand()-noise VHS build with CRTHIP_F_VHS_DRAW_ABERRATION in the single-set call,
+ * CRTHIP_F_VHS_LCG_NOISE in both); whatever it refuses is refused, and so are -- as in crthip_fieldpass_knobs -- CRTHIP_SYSTEM_PV1K,
+ * an env whose magic or n does not match, and both phosphor flags at once (CRTHIP_E_ARG, crthip_error_string says why; d_out and
+ * d_state untouched).  The launch sequence is the uniform call's: the number of launches and host synchronisations does not depend
+ * on how many distinct knob values there are.  Nothing of the call survives it: the uniform entry points behave as before.
+ */
+int  crthip_sequence_knobs(crthip_ctx *ctx, const crthip_params *p, int n,
+                           const void *d_images, size_t image_stride,
+                           void *d_out, size_t out_stride, const void *d_out_init,
+                           crthip_state *d_state,
+                           const crthip_knob_rec *d_recs /* n, DEVICE */, const crthip_knobs_env *env /* host */, int *passes);
+int  crthip_sequence_sets_knobs(crthip_ctx *ctx, const crthip_params *p,
+                                int n_sets, const int *set_first,
+                                const void *d_images, size_t image_stride,
+                                void *d_out, size_t out_stride,
+                                const void *d_out_init, size_t out_init_stride,
+                                crthip_state *d_state,
+                                const crthip_knob_rec *d_recs /* n, DEVICE */, const crthip_knobs_env *env /* host */, int *passes);
+
+/*
  * STILLS: finished still pictures for a batch of n images -- what the reference's main program does for one image
  * (`ntsc -op 640 480 0 0 in.ppm out.ppm`; the accumulate loop of crt_main.c:241-255 with blend = 1, scanlines = 1): several
  * field-passes over the SAME image onto the SAME output buffer, 4 when progressive, 8 when interlaced.
@@ -426,6 +458,13 @@ int  crthip_seq_sync(crthip_ctx *ctx, const crthip_params *p, int n, crthip_stat
 int  crthip_seq_decode(crthip_ctx *ctx, const crthip_params *p, int n, void *d_out, size_t out_stride, crthip_state *d_state);
 int  crthip_seq_weave(crthip_ctx *ctx, const crthip_params *p, int n, void *d_out, size_t out_stride,
                       const void *d_out_init, int patch_only);
+/* Per-field knobs for hosts that drive the phases themselves (one video cut over contexts): the records of THIS shard's n fields,
+ * record k = field first_index + k of the video, and the env of the crthip_knobs_prepare call that made them (copied; the records
+ * stay the caller's DEVICE memory and are read when the kernels run).  (NULL, NULL) unbinds.  Read by crthip_seq_encode / _sync /
+ * _decode only, each of which then requires env->n == n and refuses what crthip_sequence_knobs refuses; crthip_sequence*,
+ * crthip_fieldpass* and crthip_stills behave exactly as before whether or not something is bound.  Refused: CRTHIP_SYSTEM_PV1K, an env
+ * that does not come from crthip_knobs_prepare. */
+int  crthip_seq_bind_knobs(crthip_ctx *ctx, const crthip_knob_rec *d_recs /* DEVICE */, const crthip_knobs_env *env /* host */);
 
 /*
  * Stage-level entry points (used by the drop-in layer, which must keep the host's

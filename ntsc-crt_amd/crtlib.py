@@ -199,6 +199,10 @@ def load_library():
     if hasattr(L, "crthip_fieldpass_knobs"):                      # (an earlier build loaded through CRTHIP_LIBDIR for an A/B run has none)
         L.crthip_knobs_prepare.argtypes = [PP, ci, C.POINTER(Knobs), C.POINTER(KnobRec), C.POINTER(KnobsEnv)]
         L.crthip_fieldpass_knobs.argtypes = [vp, PP, ci, vp, sz, vp, sz, vp, vp, C.POINTER(KnobsEnv)]
+    if hasattr(L, "crthip_sequence_knobs"):                       # (likewise)
+        L.crthip_sequence_knobs.argtypes = [vp, PP, ci, vp, sz, vp, sz, vp, vp, vp, C.POINTER(KnobsEnv), C.POINTER(ci)]
+        L.crthip_sequence_sets_knobs.argtypes = [vp, PP, ci, C.POINTER(ci), vp, sz, vp, sz, vp, sz, vp, vp, C.POINTER(KnobsEnv), C.POINTER(ci)]
+        L.crthip_seq_bind_knobs.argtypes = [vp, vp, C.POINTER(KnobsEnv)]
     _LIB = L
     return L
 
@@ -547,11 +551,29 @@ class CRT:
         s.initialized = 1
         return passes.value
 
-    def sequence_sets(self, s, noise, set_first, out_init=None):
-        """Many television sets in one call: set i = the consecutive fields [set_first[i], set_first[i + 1]) of the batch
-        (``set_first``: n_sets + 1 ints from 0 to n, strictly ascending), each processed as ``sequence`` would process it alone.
-        ``self.state[set_first[i]]`` holds set i's hsync / vsync / rn before its first field; ``out_init``: None (zeros), one
-        picture [outh, outw, bpp] shared by all sets, or [n_sets, outh, outw, bpp]; returns the passes of the joint sync fixed point."""
+    def sequence_knobs(self, s, knobs, out_init=None, params=None):
+        """``sequence`` with per-field (noise, mon_hue, saturation): one running television set whose knobs are turned between
+        fields (crt_main.c:351-391).  ``knobs`` = (n, 3) integer array or tensor (None: the records and bounds of the last
+        upload_knobs); the uniform rest comes from ``params`` (or this CRT's settings), whose own noise, mon_hue and saturation
+        are ignored.  Returns the number of sync fixed-point passes."""
+        p = params if params is not None else self.params(s, 0)
+        if params is None:
+            self._load_field_state(s)
+        if knobs is not None:
+            self.upload_knobs(knobs, p)
+        if self.knob_recs is None:
+            raise ValueError("sequence_knobs(s, None): no knobs uploaded yet (upload_knobs)")
+        passes = C.c_int(0)
+        rc = self.L.crthip_sequence_knobs(self.ctx, C.byref(p), self.n, C.c_void_p(s.data.data_ptr()), self._image_stride(s),
+                                          C.c_void_p(self.out.data_ptr()), self.out.stride(0),
+                                          C.c_void_p(out_init.data_ptr()) if out_init is not None else None,
+                                          C.c_void_p(self.state.data_ptr()),
+                                          C.c_void_p(self.knob_recs.data_ptr()), C.byref(self._knob_env), C.byref(passes))
+        self._check(rc, "crthip_sequence_knobs")
+        s.initialized = 1
+        return passes.value
+
+    def _sets_args(self, set_first, out_init):
         first = [int(v) for v in set_first]
         n_sets = len(first) - 1
         if n_sets < 1 or first[-1] != self.n:
@@ -564,6 +586,14 @@ class CRT:
                     raise ValueError("out_init holds %d pictures for %d sets" % (int(out_init.shape[0]), n_sets))
                 init_stride = out_init.stride(0)
             init_ptr = C.c_void_p(out_init.data_ptr())
+        return first, n_sets, init_ptr, init_stride
+
+    def sequence_sets(self, s, noise, set_first, out_init=None):
+        """Many television sets in one call: set i = the consecutive fields [set_first[i], set_first[i + 1]) of the batch
+        (``set_first``: n_sets + 1 ints from 0 to n, strictly ascending), each processed as ``sequence`` would process it alone.
+        ``self.state[set_first[i]]`` holds set i's hsync / vsync / rn before its first field; ``out_init``: None (zeros), one
+        picture [outh, outw, bpp] shared by all sets, or [n_sets, outh, outw, bpp]; returns the passes of the joint sync fixed point."""
+        first, n_sets, init_ptr, init_stride = self._sets_args(set_first, out_init)
         p = self.params(s, noise)
         self._load_field_state(s)
         passes = C.c_int(0)
@@ -574,6 +604,42 @@ class CRT:
         self._check(rc, "crthip_sequence_sets")
         s.initialized = 1
         return passes.value
+
+    def sequence_sets_knobs(self, s, knobs, set_first, out_init=None, params=None):
+        """``sequence_sets`` with per-field (noise, mon_hue, saturation): ``knobs`` = (n, 3), row k = field k of the batch whatever
+        its set (None: the last upload_knobs); equals ``sequence_knobs`` per set on the set's slice of images, state and knobs."""
+        first, n_sets, init_ptr, init_stride = self._sets_args(set_first, out_init)
+        p = params if params is not None else self.params(s, 0)
+        if params is None:
+            self._load_field_state(s)
+        if knobs is not None:
+            self.upload_knobs(knobs, p)
+        if self.knob_recs is None:
+            raise ValueError("sequence_sets_knobs(s, None, ...): no knobs uploaded yet (upload_knobs)")
+        passes = C.c_int(0)
+        rc = self.L.crthip_sequence_sets_knobs(self.ctx, C.byref(p), n_sets, (C.c_int * (n_sets + 1))(*first),
+                                               C.c_void_p(s.data.data_ptr()), self._image_stride(s),
+                                               C.c_void_p(self.out.data_ptr()), self.out.stride(0), init_ptr, init_stride,
+                                               C.c_void_p(self.state.data_ptr()),
+                                               C.c_void_p(self.knob_recs.data_ptr()), C.byref(self._knob_env), C.byref(passes))
+        self._check(rc, "crthip_sequence_sets_knobs")
+        s.initialized = 1
+        return passes.value
+
+    def seq_bind_knobs(self, knobs, params=None):
+        """Per-field knobs for the phases (seq_encode / seq_sync / seq_decode) of THIS object's n fields: ``knobs`` = (n, 3), row k =
+        field first_index + k of the video; None unbinds.  ``params``: the blob the records are prepared for (default: this CRT's
+        monitor settings -- the records and bounds depend on nothing else).  sequence(), fieldpass() etc. ignore the binding."""
+        if knobs is None:
+            self._check(self.L.crthip_seq_bind_knobs(self.ctx, None, None), "crthip_seq_bind_knobs")
+            return
+        p = params if params is not None else make_params(
+            self.system, w=1, h=1, outw=self.outw, outh=self.outh, out_format=self.out_format,
+            mon_hue=self.hue, brightness=self.brightness, contrast=self.contrast, saturation=self.saturation,
+            black_point=self.black_point, white_point=self.white_point, scanlines=self.scanlines,
+            blend=self.blend, v_fac=self.v_fac, noise=0, flags=self.eq_fir << 8)
+        env = self.upload_knobs(knobs, p)
+        self._check(self.L.crthip_seq_bind_knobs(self.ctx, C.c_void_p(self.knob_recs.data_ptr()), C.byref(env)), "crthip_seq_bind_knobs")
 
     # the phases of sequence(), for a video cut over several CRT objects / ranks (shard.sequence_sharded)
     def seq_encode(self, s, noise, first_index, rn0):

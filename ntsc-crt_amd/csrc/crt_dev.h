@@ -429,10 +429,10 @@ __device__ __forceinline__ unsigned lcg_at(const uint2 *__restrict__ jump16, uns
     return rn;
 }
 
-/* Per-field knobs (crthip_fieldpass_knobs).  The kernels that apply the channel noise or fold the monitor hue and saturation into the
+/* Per-field knobs (crthip_fieldpass_knobs, crthip_sequence_knobs / _sets_knobs, the phases after crthip_seq_bind_knobs).  The kernels that apply the channel noise or fold the monitor hue and saturation into the
  * line table have a second instantiation, KN, that takes the value from the field's crthip_knob_rec instead of the parameter blob.
  * Their signatures do not change: the blob a knob launch passes is the library's own copy, whose `reserved` words carry the device
- * pointer to the record of the launch's field 0 (crt_host.hip, fieldpass_chunk), and whose noise / saturation are the batch's
+ * pointer to the record of the launch's field 0 (crt_host.hip, fieldpass_chunk / knobs_blob), and whose noise / saturation are the batch's
  * bounds -- what the launch code decides by.  crthip_ctx.knob_recs != nullptr says that such a call is under way. */
 static inline void knob_blob_set(crthip_params *q, const crthip_knob_rec *d_recs)
 {
@@ -597,8 +597,10 @@ struct crthip_ctx {
     int last_fstage;            /* the last decoder call launched the float-stage kernels (crthip_float_stages_used) */
     int sig_tile_env;           /* CRTHIP_SIG_TILE = 16 | 32 | 64: pins k_active's small / large signal tile (A/B measurements); 0 = by batch size */
     int overlap_chunks;         /* crthip_fieldpass: chunks alternating between two streams (1 = off) */
-    const crthip_knob_rec *knob_recs;   /* crthip_fieldpass_knobs under way: the caller's device records (field 0 of the batch), else nullptr */
+    const crthip_knob_rec *knob_recs;   /* a *_knobs call (or a phase with bound records) under way: the caller's device records (field 0 of the call), else nullptr */
     int knob_loskip;            /* ... and its crthip_knobs_env.loskip_wave_max */
+    const crthip_knob_rec *seq_knob_recs;   /* crthip_seq_bind_knobs: the shard's records for crthip_seq_encode / _sync / _decode (nullptr: none bound) */
+    crthip_knobs_env seq_knob_env;          /* ... and the library's copy of their bounds */
     hipStream_t aux_stream;
     hipEvent_t ev_fork, ev_join, ev_chunk[CRTHIP_MAX_CHUNKS];
     hipEvent_t ev_mfork, ev_mjoin;   /* the margin kernel beside the active-video kernel (crt_encode.hip, launch_encoder) */

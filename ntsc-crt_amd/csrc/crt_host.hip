@@ -1064,11 +1064,13 @@ int crthip_fieldpass(crthip_ctx *c, const crthip_params *p, int n, const void *d
     return fieldpass_body(c, p, n, d_images, istride, d_out, ostride, d_state);
 }
 
-int crthip_fieldpass_knobs(crthip_ctx *c, const crthip_params *p, int n, const void *d_images, size_t istride,
-                           void *d_out, size_t ostride, crthip_state *d_state, const crthip_knob_rec *d_recs, const crthip_knobs_env *env)
+/* What every per-field-knob entry point checks (p went through check_params), and *q = the blob its launch code decides by: the
+ * call's bounds where that code reads the uniform values (noise != 0, the encoder's 24-bit envelope), the device pointer to the
+ * record of the call's field 0 (knob_blob_set) for the KN kernels -- mon_hue / huesn / huecs / bloom_max_e are read by them alone,
+ * from the records -- and c->knob_loskip = the sync chain's no-low-cascade bound.  The caller sets c->knob_recs for the duration of
+ * its launches and clears it on every way out. */
+static int knobs_blob(crthip_ctx *c, const crthip_params *p, int n, const crthip_knob_rec *d_recs, const crthip_knobs_env *env, crthip_params *q)
 {
-    int rc = check_params(c, p, n);
-    if (rc) return rc;
     if (!d_recs || !env) return CRTHIP_E_ARG;
     if (env->magic != CRTHIP_KNOBS_MAGIC) return set_err(c, CRTHIP_E_ARG, "knobs: env does not come from crthip_knobs_prepare", hipSuccess);
     if (env->n != n) return set_err(c, CRTHIP_E_ARG, "knobs: env was prepared for another number of fields", hipSuccess);
@@ -1077,12 +1079,22 @@ int crthip_fieldpass_knobs(crthip_ctx *c, const crthip_params *p, int n, const v
     if (c->sd.cc_samples == 5)
         return set_err(c, CRTHIP_E_ARG, "knobs: the 5-sample decoder (PV-1000) takes monitor hue and saturation from the uniform parameters", hipSuccess);
     if (env->noise_max < 0 || env->sat_abs_max < 0) return set_err(c, CRTHIP_E_ARG, "knobs: env bounds", hipSuccess);
-    /* the blob the launch code decides by: the batch's bounds where it reads the uniform values (noise != 0, the encoder's 24-bit
-     * envelope); mon_hue / huesn / huecs / bloom_max_e are read by the KN kernels alone, from the records */
-    crthip_params q = *p;
-    q.noise = env->noise_max;
-    q.saturation = env->sat_abs_max;
+    *q = *p;
+    q->noise = env->noise_max;
+    q->saturation = env->sat_abs_max;
+    knob_blob_set(q, d_recs);
     c->knob_loskip = env->loskip_wave_max < LOSKIP_WAVE_MAX ? LOSKIP_WAVE_MAX : env->loskip_wave_max > T0_WAVE_MAX ? T0_WAVE_MAX : env->loskip_wave_max;
+    return CRTHIP_OK;
+}
+
+int crthip_fieldpass_knobs(crthip_ctx *c, const crthip_params *p, int n, const void *d_images, size_t istride,
+                           void *d_out, size_t ostride, crthip_state *d_state, const crthip_knob_rec *d_recs, const crthip_knobs_env *env)
+{
+    int rc = check_params(c, p, n);
+    if (rc) return rc;
+    crthip_params q;
+    rc = knobs_blob(c, p, n, d_recs, env, &q);
+    if (rc) return rc;
     c->knob_recs = d_recs;
     rc = fieldpass_body(c, &q, n, d_images, istride, d_out, ostride, d_state);
     c->knob_recs = nullptr;
@@ -1314,8 +1326,12 @@ static int seq_check(crthip_ctx *c, const crthip_params *p, int n)
     return CRTHIP_OK;
 }
 
+/* The phases.  Each *_body runs with the blob it is given: the caller's p, or -- c->knob_recs set: crthip_sequence_knobs, or a phase
+ * entry point with bound records -- the library's copy of knobs_blob, whose KN kernels then read noise, monitor hue and saturation
+ * (and bloom's max_e) per field.  Nothing of sequence mode's own arithmetic changes with that: rn advances once per sample whatever
+ * the gain (crt_core.c:358-366, so k_seq_rn's closed form holds), and the sync fixed point reads only the noisy signal. */
 /* phase 1: the noise generator of every field in closed form, all fields encoded in parallel (noise fused) */
-int crthip_seq_encode(crthip_ctx *c, const crthip_params *p, int n, int first_index, int rn0,
+static int seq_encode_body(crthip_ctx *c, const crthip_params *p, int n, int first_index, int rn0,
                       const void *d_images, size_t istride, crthip_state *d_state)
 {
     int rc = seq_check(c, p, n);
@@ -1366,8 +1382,8 @@ int crthip_seq_encode(crthip_ctx *c, const crthip_params *p, int n, int first_in
  * incoming pair (a video cut over several shards: the predecessor's final state became known) it restarts from the
  * finals of the previous call, so only the fields whose state really depends on the incoming pair are recomputed
  * in more than one pass. */
-int crthip_seq_sync(crthip_ctx *c, const crthip_params *p, int n, crthip_state *d_state, int hsync_in, int vsync_in,
-                    int *hsync_out, int *vsync_out, int *passes_out)
+static int seq_sync_body(crthip_ctx *c, const crthip_params *p, int n, crthip_state *d_state, int hsync_in, int vsync_in,
+                         int *hsync_out, int *vsync_out, int *passes_out)
 {
     int rc = seq_check(c, p, n);
     if (rc) return rc;
@@ -1389,7 +1405,8 @@ int crthip_seq_sync(crthip_ctx *c, const crthip_params *p, int n, crthip_state *
         c->seq_guess_n = n;
     }
     int passes = 0;
-    const crthip_params q = with_signal_envelope(p);                  /* inp[] comes from crthip_seq_encode */
+    crthip_params q = c->knob_recs ? *p : with_signal_envelope(p);    /* inp[] comes from crthip_seq_encode */
+    if (c->knob_recs) q.loskip_wave_max = c->knob_loskip;             /* the envelope at the widest noise of the records (crthip_knobs_prepare) */
     for (;;) {
         passes++;
         HIPCHK(c, hipMemsetAsync(sc.changed, 0, sizeof(int), c->stream));
@@ -1418,7 +1435,7 @@ int crthip_seq_sync(crthip_ctx *c, const crthip_params *p, int n, crthip_state *
 }
 
 /* phase 3: rn after each field, all fields decoded in parallel (without blend: phase 4 folds the fields) */
-int crthip_seq_decode(crthip_ctx *c, const crthip_params *p, int n, void *d_out, size_t ostride, crthip_state *d_state)
+static int seq_decode_body(crthip_ctx *c, const crthip_params *p, int n, void *d_out, size_t ostride, crthip_state *d_state)
 {
     int rc = seq_check(c, p, n);
     if (rc) return rc;
@@ -1505,8 +1522,75 @@ int crthip_seq_vhs_prechained(crthip_ctx *c, int on)
     return CRTHIP_OK;
 }
 
-int crthip_sequence(crthip_ctx *c, const crthip_params *p, int n, const void *d_images, size_t istride,
-                    void *d_out, size_t ostride, const void *d_out_init, crthip_state *d_state, int *passes_out)
+/* The phase entry points.  Records bound with crthip_seq_bind_knobs: the phase runs on the library's copy of the blob (knobs_blob)
+ * with c->knob_recs set for its duration; nothing bound: exactly the uniform phase.  c->knob_recs is cleared on every way out. */
+static int seq_phase_blob(crthip_ctx *c, const crthip_params *p, int n, crthip_params *q, const crthip_params **use)
+{
+    *use = p;
+    if (!c) return CRTHIP_OK;                             /* (refused by the body) */
+    c->knob_recs = nullptr;
+    if (!c->seq_knob_recs) return CRTHIP_OK;
+    int rc = check_params(c, p, n);
+    if (rc) return rc;
+    rc = knobs_blob(c, p, n, c->seq_knob_recs, &c->seq_knob_env, q);
+    if (rc) return rc;
+    c->knob_recs = c->seq_knob_recs;
+    *use = q;
+    return CRTHIP_OK;
+}
+
+int crthip_seq_bind_knobs(crthip_ctx *c, const crthip_knob_rec *d_recs, const crthip_knobs_env *env)
+{
+    if (!c) return CRTHIP_E_ARG;
+    if (!d_recs && !env) { c->seq_knob_recs = nullptr; return CRTHIP_OK; }
+    if (!d_recs || !env) return set_err(c, CRTHIP_E_ARG, "crthip_seq_bind_knobs: records and env go together ((NULL, NULL) unbinds)", hipSuccess);
+    if (env->magic != CRTHIP_KNOBS_MAGIC) return set_err(c, CRTHIP_E_ARG, "knobs: env does not come from crthip_knobs_prepare", hipSuccess);
+    if (c->sd.cc_samples == 5)
+        return set_err(c, CRTHIP_E_ARG, "knobs: the 5-sample decoder (PV-1000) takes monitor hue and saturation from the uniform parameters", hipSuccess);
+    if (env->n <= 0 || env->noise_max < 0 || env->sat_abs_max < 0) return set_err(c, CRTHIP_E_ARG, "knobs: env bounds", hipSuccess);
+    c->seq_knob_recs = d_recs;
+    c->seq_knob_env = *env;
+    return CRTHIP_OK;
+}
+
+int crthip_seq_encode(crthip_ctx *c, const crthip_params *p, int n, int first_index, int rn0,
+                      const void *d_images, size_t istride, crthip_state *d_state)
+{
+    crthip_params q;
+    const crthip_params *use;
+    int rc = seq_phase_blob(c, p, n, &q, &use);
+    if (rc) return rc;
+    rc = seq_encode_body(c, use, n, first_index, rn0, d_images, istride, d_state);
+    if (c) c->knob_recs = nullptr;
+    return rc;
+}
+
+int crthip_seq_sync(crthip_ctx *c, const crthip_params *p, int n, crthip_state *d_state, int hsync_in, int vsync_in,
+                    int *hsync_out, int *vsync_out, int *passes_out)
+{
+    crthip_params q;
+    const crthip_params *use;
+    int rc = seq_phase_blob(c, p, n, &q, &use);
+    if (rc) return rc;
+    rc = seq_sync_body(c, use, n, d_state, hsync_in, vsync_in, hsync_out, vsync_out, passes_out);
+    if (c) c->knob_recs = nullptr;
+    return rc;
+}
+
+int crthip_seq_decode(crthip_ctx *c, const crthip_params *p, int n, void *d_out, size_t ostride, crthip_state *d_state)
+{
+    crthip_params q;
+    const crthip_params *use;
+    int rc = seq_phase_blob(c, p, n, &q, &use);
+    if (rc) return rc;
+    rc = seq_decode_body(c, use, n, d_out, ostride, d_state);
+    if (c) c->knob_recs = nullptr;
+    return rc;
+}
+
+/* crthip_sequence, and crthip_sequence_knobs when c->knob_recs is set (p is then the library's copy carrying the call's bounds) */
+static int sequence_body(crthip_ctx *c, const crthip_params *p, int n, const void *d_images, size_t istride,
+                         void *d_out, size_t ostride, const void *d_out_init, crthip_state *d_state, int *passes_out)
 {
     int rc = check_params(c, p, n);
     if (rc) return rc;
@@ -1516,13 +1600,36 @@ int crthip_sequence(crthip_ctx *c, const crthip_params *p, int n, const void *d_
     crthip_state first;
     HIPCHK(c, hipMemcpyAsync(&first, d_state, sizeof(first), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    rc = crthip_seq_encode(c, p, n, 0, first.rn, d_images, istride, d_state);
+    rc = seq_encode_body(c, p, n, 0, first.rn, d_images, istride, d_state);
     if (rc) return rc;
-    rc = crthip_seq_sync(c, p, n, d_state, first.hsync, first.vsync, nullptr, nullptr, passes_out);
+    rc = seq_sync_body(c, p, n, d_state, first.hsync, first.vsync, nullptr, nullptr, passes_out);
     if (rc) return rc;
-    rc = crthip_seq_decode(c, p, n, d_out, ostride, d_state);
+    rc = seq_decode_body(c, p, n, d_out, ostride, d_state);
     if (rc) return rc;
     return crthip_seq_weave(c, p, n, d_out, ostride, d_out_init, 0);
+}
+
+int crthip_sequence(crthip_ctx *c, const crthip_params *p, int n, const void *d_images, size_t istride,
+                    void *d_out, size_t ostride, const void *d_out_init, crthip_state *d_state, int *passes_out)
+{
+    if (c) c->knob_recs = nullptr;
+    return sequence_body(c, p, n, d_images, istride, d_out, ostride, d_out_init, d_state, passes_out);
+}
+
+int crthip_sequence_knobs(crthip_ctx *c, const crthip_params *p, int n, const void *d_images, size_t istride,
+                          void *d_out, size_t ostride, const void *d_out_init, crthip_state *d_state,
+                          const crthip_knob_rec *d_recs, const crthip_knobs_env *env, int *passes_out)
+{
+    int rc = check_params(c, p, n);
+    if (rc) return rc;
+    c->knob_recs = nullptr;
+    crthip_params q;
+    rc = knobs_blob(c, p, n, d_recs, env, &q);
+    if (rc) return rc;
+    c->knob_recs = d_recs;
+    rc = sequence_body(c, &q, n, d_images, istride, d_out, ostride, d_out_init, d_state, passes_out);
+    c->knob_recs = nullptr;
+    return rc;
 }
 
 /* scratch of crthip_sequence_sets (the same lazily grown block as seq_scratch): set_first[n_sets + 1], tab[n] (first field of my
@@ -1552,9 +1659,12 @@ static int sets_scratch(crthip_ctx *c, int n_sets, int n, int outh, SetsScratch 
     return CRTHIP_OK;
 }
 
-int crthip_sequence_sets(crthip_ctx *c, const crthip_params *p, int n_sets, const int *set_first,
-                         const void *d_images, size_t istride, void *d_out, size_t ostride,
-                         const void *d_out_init, size_t out_init_stride, crthip_state *d_state, int *passes_out)
+/* crthip_sequence_sets, and crthip_sequence_sets_knobs when d_recs is given: the call then runs on the library's copy of the blob
+ * (knobs_blob over all n fields: record k belongs to field k of the batch, whatever its set) with c->knob_recs set by the caller */
+static int sequence_sets_body(crthip_ctx *c, const crthip_params *p, int n_sets, const int *set_first,
+                              const void *d_images, size_t istride, void *d_out, size_t ostride,
+                              const void *d_out_init, size_t out_init_stride, crthip_state *d_state, int *passes_out,
+                              const crthip_knob_rec *d_recs, const crthip_knobs_env *env)
 {
     if (!c || !p) return CRTHIP_E_ARG;
     if (n_sets <= 0 || !set_first) return set_err(c, CRTHIP_E_ARG, "crthip_sequence_sets: no sets", hipSuccess);
@@ -1577,6 +1687,12 @@ int crthip_sequence_sets(crthip_ctx *c, const crthip_params *p, int n_sets, cons
         return set_err(c, CRTHIP_E_ARG, "crthip_sequence_sets: CRTHIP_F_VHS_DRAW_ABERRATION draws from the rand() stream; give the heights in d_state[k].aux", hipSuccess);
     rc = seq_check(c, p, n);
     if (rc) return rc;
+    crthip_params pk;
+    if (c->knob_recs) {
+        rc = knobs_blob(c, p, n, d_recs, env, &pk);
+        if (rc) return rc;
+        p = &pk;
+    }
     HIPCHK(c, hipSetDevice(c->device));
     if (n > c->cap_fields) {
         rc = crthip_reserve(c, n);
@@ -1612,7 +1728,8 @@ int crthip_sequence_sets(crthip_ctx *c, const crthip_params *p, int n_sets, cons
     if (rc) return rc;
     /* the joint fixed point: one flag for all sets; after pass j the first j fields of every set are final */
     int passes = 0;
-    const crthip_params q = with_signal_envelope(p);
+    crthip_params q = c->knob_recs ? *p : with_signal_envelope(p);
+    if (c->knob_recs) q.loskip_wave_max = c->knob_loskip;
     for (;;) {
         passes++;
         HIPCHK(c, hipMemsetAsync(sc.changed, 0, sizeof(int), c->stream));
@@ -1654,6 +1771,29 @@ int crthip_sequence_sets(crthip_ctx *c, const crthip_params *p, int n_sets, cons
     c->last_lay.pitch = c->sd.hres; c->last_lay.shift = 0; c->last_lay.padv = 0; c->last_lay.wrap = 0; c->last_lay.fstride = c->fstride;
     c->last_n = n;
     return CRTHIP_OK;
+}
+
+int crthip_sequence_sets(crthip_ctx *c, const crthip_params *p, int n_sets, const int *set_first,
+                         const void *d_images, size_t istride, void *d_out, size_t ostride,
+                         const void *d_out_init, size_t out_init_stride, crthip_state *d_state, int *passes_out)
+{
+    if (c) c->knob_recs = nullptr;
+    return sequence_sets_body(c, p, n_sets, set_first, d_images, istride, d_out, ostride, d_out_init, out_init_stride, d_state, passes_out,
+                              nullptr, nullptr);
+}
+
+int crthip_sequence_sets_knobs(crthip_ctx *c, const crthip_params *p, int n_sets, const int *set_first,
+                               const void *d_images, size_t istride, void *d_out, size_t ostride,
+                               const void *d_out_init, size_t out_init_stride, crthip_state *d_state,
+                               const crthip_knob_rec *d_recs, const crthip_knobs_env *env, int *passes_out)
+{
+    if (!c || !p) return CRTHIP_E_ARG;
+    if (!d_recs || !env) return set_err(c, CRTHIP_E_ARG, "crthip_sequence_sets_knobs: no records / env", hipSuccess);
+    c->knob_recs = d_recs;
+    const int rc = sequence_sets_body(c, p, n_sets, set_first, d_images, istride, d_out, ostride, d_out_init, out_init_stride, d_state,
+                                      passes_out, d_recs, env);
+    c->knob_recs = nullptr;
+    return rc;
 }
 
 int crthip_set_shape(crthip_ctx *c, int shape)
