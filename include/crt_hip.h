@@ -113,6 +113,10 @@ extern "C" {
  * _decode) refuse both flags: there the host owns the buffer, as crt_main.c does.  crthip_params_finalize refuses both at once. */
 #define CRTHIP_F_PHOSPHOR_FADE  0x8000
 #define CRTHIP_F_PHOSPHOR_CLEAR 0x10000
+/* crthip_sequence_sets / _sets_knobs on the stock VHS build (CRTHIP_SYSTEM_NTSCVHS without CRTHIP_F_VHS_LCG_NOISE): every set owns
+ * ONE rand() stream, entry set_first[s] of the bound history array is set s's generator before its first field (see there).
+ * Every other entry point ignores the flag; crthip_params_finalize refuses it on another system and with CRTHIP_F_VHS_LCG_NOISE. */
+#define CRTHIP_F_VHS_SET_STREAMS 0x20000
 
 /*
  * Everything that is uniform over a batch of field-passes.  Plain old data, no
@@ -340,9 +344,16 @@ int  crthip_sequence(crthip_ctx *ctx, const crthip_params *p, int n,
  *   d_out_init + s * out_init_stride = set s's output buffer before its first field; out_init_stride == 0: one picture shared
  *   by all sets; d_out_init == NULL: zeros.
  *   *passes (optional) = passes of the joint sync fixed point (one pass covers all sets; at most the longest set's length + 1).
- * Refused (CRTHIP_E_ARG, crthip_error_string says why): anything else in set_first; what crthip_sequence refuses; the VHS build
- * with rand() noise (CRTHIP_SYSTEM_NTSCVHS without CRTHIP_F_VHS_LCG_NOISE: every set would own a rand() stream) and
- * CRTHIP_F_VHS_DRAW_ABERRATION, which draws from that stream (give the aberration heights in d_state[k].aux).
+ * The VHS build with rand() noise (CRTHIP_SYSTEM_NTSCVHS without CRTHIP_F_VHS_LCG_NOISE) takes CRTHIP_F_VHS_SET_STREAMS: every set
+ * owns one rand() stream.  Entry set_first[s] of the bound history array (crthip_vhs_bind_history, n x 32 words) is set s's
+ * generator before its first field, read on the device (the other entries are ignored on input); the sets' chains are walked side
+ * by side, one wavefront per set, so the serial pre-pass of crthip_sequence costs the longest set's length, not the batch's.  On
+ * return entry k is the generator after field k and d_state[k].rn the last value drawn (the incoming .rn is not used); with
+ * CRTHIP_F_VHS_DRAW_ABERRATION every field's aberration height is drawn from its own set's stream and left in d_state[k].aux.
+ * Again what crthip_sequence gives per set, on the set's slice of the history array as well.
+ * Refused (CRTHIP_E_ARG, crthip_error_string says why): anything else in set_first; what crthip_sequence refuses; without
+ * CRTHIP_F_VHS_SET_STREAMS the VHS build with rand() noise (every set would own a rand() stream) and CRTHIP_F_VHS_DRAW_ABERRATION,
+ * which draws from that stream (give the aberration heights in d_state[k].aux); with it, no history array bound.
  */
 int  crthip_sequence_sets(crthip_ctx *ctx, const crthip_params *p,
                           int n_sets, const int *set_first,

@@ -22,6 +22,8 @@ F_NES_SETUP, F_VHS_DRAW_ABERRATION, F_BLOOM, F_IMAGE_SPARE_ROW = 2, 4, 8, 16
 F_NO_HSYNC, F_NO_VSYNC, F_VHS_LCG_NOISE, F_HIPASS, F_VHS_LP, F_VHS_EP, F_NES_BORDER = 0x20, 0x40, 0x80, 0x800, 0x2000, 0x4000, 0x1000
 # display modes of crt_main.c's displaycb (crt_main.c:459-463): fade the phosphors / clear the display before every field
 F_PHOSPHOR_FADE, F_PHOSPHOR_CLEAR = 0x8000, 0x10000
+# sequence_sets on the stock VHS build: one rand() stream per set (vhs_hist[set_first[s]] = set s's generator before its first field)
+F_VHS_SET_STREAMS = 0x20000
 PHOSPHOR_FLAGS = {"keep": 0, "fade": F_PHOSPHOR_FADE, "clear": F_PHOSPHOR_CLEAR}
 K_NAMES = ("template", "active", "noise", "sync", "decode")
 MAX_VPER, MAX_CCS, CARRIER_ROWS = 5, 5, 10
@@ -388,14 +390,14 @@ class CRT:
             self._lines = self.torch.zeros((self.n, self.lines, LINE_INTS), dtype=self.torch.int32, device=self.dev)
         return self._lines
 
-    def params(self, s, noise=0):
-        """The batch-uniform parameter blob for settings ``s`` and this CRT's knobs."""
+    def params(self, s, noise=0, flags=0):
+        """The batch-uniform parameter blob for settings ``s`` and this CRT's knobs (``flags``: further CRTHIP_F_* bits)."""
         d = s.data
         if self.sysid == SYSTEM_NES:
             h, w = int(d.shape[1]), int(d.shape[2])
         else:
             h, w = int(d.shape[1]), int(d.shape[2])
-        flags = self.eq_fir << 8                                   # CRTHIP_F_EQ_FIR(taps)
+        flags |= self.eq_fir << 8                                  # CRTHIP_F_EQ_FIR(taps)
         if self.phosphor not in PHOSPHOR_FLAGS:
             raise ValueError("CRT.phosphor must be one of %s, not %r" % (sorted(PHOSPHOR_FLAGS), self.phosphor))
         flags |= PHOSPHOR_FLAGS[self.phosphor]
@@ -588,13 +590,15 @@ class CRT:
             init_ptr = C.c_void_p(out_init.data_ptr())
         return first, n_sets, init_ptr, init_stride
 
-    def sequence_sets(self, s, noise, set_first, out_init=None):
+    def sequence_sets(self, s, noise, set_first, out_init=None, vhs_streams=False):
         """Many television sets in one call: set i = the consecutive fields [set_first[i], set_first[i + 1]) of the batch
         (``set_first``: n_sets + 1 ints from 0 to n, strictly ascending), each processed as ``sequence`` would process it alone.
         ``self.state[set_first[i]]`` holds set i's hsync / vsync / rn before its first field; ``out_init``: None (zeros), one
-        picture [outh, outw, bpp] shared by all sets, or [n_sets, outh, outw, bpp]; returns the passes of the joint sync fixed point."""
+        picture [outh, outw, bpp] shared by all sets, or [n_sets, outh, outw, bpp]; returns the passes of the joint sync fixed point.
+        ``vhs_streams`` (the stock "vhs" build): every set owns one rand() stream, ``vhs_hist[set_first[i]]`` (``srand``) is set i's
+        generator before its first field; ``s.draw_aberration`` then draws every field's aberration height from its set's stream."""
         first, n_sets, init_ptr, init_stride = self._sets_args(set_first, out_init)
-        p = self.params(s, noise)
+        p = self.params(s, noise, F_VHS_SET_STREAMS if vhs_streams else 0)
         self._load_field_state(s)
         passes = C.c_int(0)
         rc = self.L.crthip_sequence_sets(self.ctx, C.byref(p), n_sets, (C.c_int * (n_sets + 1))(*first),
@@ -605,11 +609,12 @@ class CRT:
         s.initialized = 1
         return passes.value
 
-    def sequence_sets_knobs(self, s, knobs, set_first, out_init=None, params=None):
+    def sequence_sets_knobs(self, s, knobs, set_first, out_init=None, params=None, vhs_streams=False):
         """``sequence_sets`` with per-field (noise, mon_hue, saturation): ``knobs`` = (n, 3), row k = field k of the batch whatever
-        its set (None: the last upload_knobs); equals ``sequence_knobs`` per set on the set's slice of images, state and knobs."""
+        its set (None: the last upload_knobs); equals ``sequence_knobs`` per set on the set's slice of images, state and knobs.
+        ``vhs_streams``: as for ``sequence_sets`` (a given ``params`` must carry F_VHS_SET_STREAMS itself)."""
         first, n_sets, init_ptr, init_stride = self._sets_args(set_first, out_init)
-        p = params if params is not None else self.params(s, 0)
+        p = params if params is not None else self.params(s, 0, F_VHS_SET_STREAMS if vhs_streams else 0)
         if params is None:
             self._load_field_state(s)
         if knobs is not None:

@@ -722,7 +722,7 @@ int crt_run_encoder_prepare(crthip_ctx *c, const crthip_params *p, bool fused);
 int crt_run_noise(crthip_ctx *c, const crthip_params *p, int n, const signed char *d_analog, signed char *d_inp,
                   crthip_state *d_state, bool advance_rn);
 int crt_run_advance_rn(crthip_ctx *c, int n, crthip_state *d_state);
-int crt_run_vhs_chain(crthip_ctx *c, int n, crthip_state *d_state, int draw_aberration);
+int crt_run_vhs_chain(crthip_ctx *c, int n, crthip_state *d_state, int draw_aberration, int n_sets = 1, const int *d_set_first = nullptr);
 int crt_run_clean_vsync(crthip_ctx *c, int n, const signed char *d_analog, crthip_state *d_state);
 int crt_run_sync(crthip_ctx *c, const crthip_params *p, int n, const signed char *d_inp, crthip_state *d_state,
                  crthip_line *d_lines, int advance_rn, int preset_ccf = 0, const sig_layout *lay = nullptr);

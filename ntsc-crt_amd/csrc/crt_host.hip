@@ -264,6 +264,15 @@ __global__ void k_sets_rn(int n_fields, crthip_state *state, const int2 *tab, co
     guess[k] = make_int2(in.x, in.y);
 }
 
+/* k_sets_rn without the generator, for the rand() streams of the VHS build (whose rn is the last value drawn: k_vhs_tail leaves it) */
+__global__ void k_sets_guess(int n_fields, const int2 *tab, const int4 *inc, int2 *guess)
+{
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n_fields) return;
+    const int4 in = inc[tab[k].y];
+    guess[k] = make_int2(in.x, in.y);
+}
+
 /* init_k = the set's incoming pair for the first field of a set, guess[k-1] otherwise */
 __global__ void k_sets_load(int n_fields, crthip_state *state, const int2 *tab, const int4 *inc, const int2 *guess)
 {
@@ -1680,12 +1689,17 @@ static int sequence_sets_body(crthip_ctx *c, const crthip_params *p, int n_sets,
     if (rc) return rc;
     if (!d_images || !d_out || !d_state) return CRTHIP_E_ARG;
     if (p->out_bpp == 0) return CRTHIP_OK;                /* as crthip_sequence */
-    if (c->system == CRTHIP_SYSTEM_NTSCVHS && !(p->flags & CRTHIP_F_VHS_LCG_NOISE))
+    /* CRTHIP_F_VHS_SET_STREAMS: every set owns one rand() stream (hist[set_first[s]] = its generator before its first field) */
+    const bool streams = (p->flags & CRTHIP_F_VHS_SET_STREAMS) != 0;
+    if (streams && (c->system != CRTHIP_SYSTEM_NTSCVHS || (p->flags & CRTHIP_F_VHS_LCG_NOISE)))
+        return set_err(c, CRTHIP_E_ARG, "crthip_sequence_sets: CRTHIP_F_VHS_SET_STREAMS is for the VHS build with rand() noise "
+                                        "(CRTHIP_SYSTEM_NTSCVHS without CRTHIP_F_VHS_LCG_NOISE)", hipSuccess);
+    if (!streams && c->system == CRTHIP_SYSTEM_NTSCVHS && !(p->flags & CRTHIP_F_VHS_LCG_NOISE))
         return set_err(c, CRTHIP_E_ARG, "crthip_sequence_sets: the VHS build with rand() noise is not available (every set would own a rand() stream); "
                                         "use CRTHIP_F_VHS_LCG_NOISE or crthip_sequence per set", hipSuccess);
-    if (c->system == CRTHIP_SYSTEM_NTSCVHS && (p->flags & CRTHIP_F_VHS_DRAW_ABERRATION))
+    if (!streams && c->system == CRTHIP_SYSTEM_NTSCVHS && (p->flags & CRTHIP_F_VHS_DRAW_ABERRATION))
         return set_err(c, CRTHIP_E_ARG, "crthip_sequence_sets: CRTHIP_F_VHS_DRAW_ABERRATION draws from the rand() stream; give the heights in d_state[k].aux", hipSuccess);
-    rc = seq_check(c, p, n);
+    rc = seq_check(c, p, n);                              /* (streams: also that a history array is bound) */
     if (rc) return rc;
     crthip_params pk;
     if (c->knob_recs) {
@@ -1723,9 +1737,24 @@ static int sequence_sets_body(crthip_ctx *c, const crthip_params *p, int n_sets,
     if (rc) return rc;
     const dim3 gn((n + 63) / 64), gs((n_sets + 63) / 64), b64(64);
     hipLaunchKernelGGL(k_sets_incoming, gs, b64, 0, c->stream, n_sets, sc.set_first, d_state, sc.inc);
-    hipLaunchKernelGGL(k_sets_rn, gn, b64, 0, c->stream, n, d_state, sc.tab, sc.inc, sc.guess, c->whole_field);
-    rc = crt_run_encoder(c, p, n, d_images, istride, c->d_inp, d_state, true, 1, false);
-    if (rc) return rc;
+    if (streams) {
+        /* as seq_encode_body for the single set: the chains ahead of everything else (k_vhs_chain<SETS>: one wave per set, hist[k] =
+         * the generator at the start of field k, the aberration heights drawn in-stream if asked), clean encode, rand() noise
+         * (which also leaves rn and the histories after every field) */
+        hipLaunchKernelGGL(k_sets_guess, gn, b64, 0, c->stream, n, sc.tab, sc.inc, sc.guess);
+        rc = crt_run_vhs_chain(c, n, d_state, (p->flags & CRTHIP_F_VHS_DRAW_ABERRATION) != 0, n_sets, sc.set_first);
+        if (rc) return rc;
+        crthip_params clean = *p;
+        clean.noise = 0;
+        rc = crt_run_encoder(c, &clean, n, d_images, istride, c->d_analog, d_state, true, 1, false);
+        if (rc) return rc;
+        rc = crt_run_noise(c, p, n, c->d_analog, c->d_inp, d_state, false);
+        if (rc) return rc;
+    } else {
+        hipLaunchKernelGGL(k_sets_rn, gn, b64, 0, c->stream, n, d_state, sc.tab, sc.inc, sc.guess, c->whole_field);
+        rc = crt_run_encoder(c, p, n, d_images, istride, c->d_inp, d_state, true, 1, false);
+        if (rc) return rc;
+    }
     /* the joint fixed point: one flag for all sets; after pass j the first j fields of every set are final */
     int passes = 0;
     crthip_params q = c->knob_recs ? *p : with_signal_envelope(p);
@@ -1747,7 +1776,7 @@ static int sequence_sets_body(crthip_ctx *c, const crthip_params *p, int n_sets,
             return set_err(c, CRTHIP_E_HIP, "crthip_sequence_sets: the sync chain over the fields did not converge", hipSuccess);
     }
     if (passes_out) *passes_out = passes;
-    crt_run_advance_rn(c, n, d_state);
+    if (!streams) crt_run_advance_rn(c, n, d_state);
     crthip_params pb = *p;
     pb.blend = 0;
     rc = crt_run_decode(c, &pb, n, c->d_inp, c->d_lines, d_out, ostride);

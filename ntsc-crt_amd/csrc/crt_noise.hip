@@ -577,11 +577,15 @@ k_vhs_tail(const crthip_params P, int n_fields, const signed char *__restrict__ 
  * one wave walks the fields in order with the same speculative block walk as k_vhs_tail minus the samples, and
  * leaves in hist[k] the generator history at the start of field k's crt_demodulate (and, if asked to, draws the
  * aberration height of crt_modulate, crt_ntscvhs.c:205-207, from the stream: one call per field, before it).
- * Afterwards every field is independent again.  Serial by nature: ~0.15 ms per field.
+ * Afterwards every field is independent again.  Serial by nature: ~0.15 ms per field (0.24 measured, profiles/vhs_sets_timing.txt).
+ * SETS (crthip_sequence_sets with CRTHIP_F_VHS_SET_STREAMS): every set owns one stream, so the chains of different sets do not
+ * depend on each other -- one workgroup (= one wave) per set walks fields [set_first[s], set_first[s + 1]) from hist[set_first[s]],
+ * and the serial part of a call is the longest set's chain.  The walk is the same code; state[] and hist[] are indexed by the
+ * field's position in the batch either way.
  */
-template <class S>
+template <class S, bool SETS = false>
 __global__ void __launch_bounds__(64)
-k_vhs_chain(int n_fields, crthip_state *__restrict__ state, unsigned *__restrict__ hist,
+k_vhs_chain(int n_fields, const int *__restrict__ set_first, crthip_state *__restrict__ state, unsigned *__restrict__ hist,
             const unsigned *__restrict__ tail_row, const unsigned *__restrict__ blk_rows, int draw_aberration)
 {
     constexpr int N = S::INPUT_SIZE, H = S::HRES, B = VHS_BLK;
@@ -594,10 +598,11 @@ k_vhs_chain(int n_fields, crthip_state *__restrict__ state, unsigned *__restrict
     unsigned cb[31];
 #pragma unroll
     for (int m = 0; m < 31; m++) cb[m] = blk_rows[m * 64 + lane];
-    if (lane < 31) s_cur[lane] = hist[lane];
+    const int f_lo = SETS ? set_first[blockIdx.x] : 0, f_hi = SETS ? set_first[blockIdx.x + 1] : n_fields;
+    if (lane < 31) s_cur[lane] = hist[(size_t) f_lo * 32 + lane];
     __syncthreads();
 
-    for (int f = 0; f < n_fields; f++) {
+    for (int f = f_lo; f < f_hi; f++) {
         if (draw_aberration) {
             /* one call: y = y[n-31] + y[n-3]; the history slides by one */
             const unsigned y = s_cur[0] + s_cur[28];
@@ -801,16 +806,21 @@ int crt_run_noise(crthip_ctx *c, const crthip_params *p, int n, const signed cha
     });
 }
 
-/* VHS sequence mode: hist[0] = the generator before field 0 -> hist[k] for every field (see k_vhs_chain) */
-int crt_run_vhs_chain(crthip_ctx *c, int n, crthip_state *d_state, int draw_aberration)
+/* VHS sequence mode: hist[0] = the generator before field 0 -> hist[k] for every field (see k_vhs_chain).  d_set_first (a DEVICE
+ * table of n_sets + 1 entries, n = its last): one stream per set, hist[set_first[s]] = set s's generator before its first field */
+int crt_run_vhs_chain(crthip_ctx *c, int n, crthip_state *d_state, int draw_aberration, int n_sets, const int *d_set_first)
 {
     if (!c->d_vhs_hist) return set_err(c, CRTHIP_E_ARG, "VHS: no generator histories bound (crthip_vhs_bind_history)", hipSuccess);
     return dispatch_system(c->system, c->pattern, [&](auto tag) {
         using S = decltype(tag);
         if constexpr (S::IS_VHS) {
-            hipLaunchKernelGGL((k_vhs_chain<S>), dim3(1), dim3(64), 0, c->stream, n, d_state, c->d_vhs_hist,
-                               c->d_vhs_rows + (size_t) c->vhs_chunks * 31, c->d_vhs_rows + (size_t) (c->vhs_chunks + 1) * 31,
-                               draw_aberration);
+            const unsigned *tail_row = c->d_vhs_rows + (size_t) c->vhs_chunks * 31, *blk_rows = c->d_vhs_rows + (size_t) (c->vhs_chunks + 1) * 31;
+            if (d_set_first)
+                hipLaunchKernelGGL((k_vhs_chain<S, true>), dim3((unsigned) n_sets), dim3(64), 0, c->stream, n, d_set_first, d_state, c->d_vhs_hist,
+                                   tail_row, blk_rows, draw_aberration);
+            else
+                hipLaunchKernelGGL((k_vhs_chain<S>), dim3(1), dim3(64), 0, c->stream, n, (const int *) nullptr, d_state, c->d_vhs_hist,
+                                   tail_row, blk_rows, draw_aberration);
         }
         return CRTHIP_OK;
     });

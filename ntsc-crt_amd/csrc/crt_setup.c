@@ -411,6 +411,9 @@ crthip_params_finalize(crthip_params *p)
     if ((p->flags & CRTHIP_F_VHS_LP) && (p->flags & CRTHIP_F_VHS_EP)) {
         return CRTHIP_E_ARG;
     }
+    if ((p->flags & CRTHIP_F_VHS_SET_STREAMS) && (p->system != CRTHIP_SYSTEM_NTSCVHS || (p->flags & CRTHIP_F_VHS_LCG_NOISE))) {
+        return CRTHIP_E_ARG;                                    /* one rand() stream per set: only the rand() build has one */
+    }
     if ((p->flags & CRTHIP_F_NES_BORDER) && p->system != CRTHIP_SYSTEM_NES) {
         return CRTHIP_E_ARG;
     }
