@@ -237,7 +237,7 @@ int  crthip_phosphor_table(int age, unsigned char lut[256]);
  * of every field as its 31-word history (the values preceding the next output), in/out, device
  * resident, 32 words apart.  crthip_vhs_history_from_seed gives the history right after srand(seed). */
 int  crthip_vhs_history_from_seed(unsigned seed, unsigned hist[31]);
-int  crthip_vhs_bind_history(crthip_ctx *ctx, unsigned *d_hist);     /* n x 32 words, device */
+int  crthip_vhs_bind_history(crthip_ctx *ctx, unsigned *d_hist);     /* n x 32 words, device, 4-byte aligned (else CRTHIP_E_ARG) */
 
 /* Context = one device + one stream + the jump tables of the noise LCG. */
 int  crthip_create(crthip_ctx **out, int device, int system, int chroma_pattern);
@@ -252,6 +252,29 @@ const char *crthip_error_string(const crthip_ctx *ctx);
 int  crthip_reserve(crthip_ctx *ctx, int n_fields);
 
 /*
+ * BUFFER CONTRACT of every device pointer argument below (DESIGN.md "Buffer contract" has the table and says which entry points
+ * tests/test_gpu_fence.py runs on fenced buffers with loose strides and offset bases).  Nothing outside the extents named here is read or
+ * written, whatever the base and the stride; an alignment this list forbids is refused with CRTHIP_E_ARG (crthip_error_string
+ * says which argument) BEFORE anything is launched, copied or reserved -- every buffer of the call is then untouched.
+ *   d_images, image_stride : image k = the w*h*bpp bytes from d_images + k*image_stride (w*h 16-bit PPU pixels for the NES), READ
+ *              ONLY; with CRTHIP_F_IMAGE_SPARE_ROW one more row (w*bpp bytes) behind each image is read as well, without it not a
+ *              byte.  image_stride >= those bytes, otherwise free (the images need not be packed).  Base AND stride: multiples of
+ *              4 for the 4-byte pixel formats (the kernels load whole pixels as dwords), of 2 for PPU pixels, any for RGB / BGR.
+ *   d_out, out_stride      : picture k = the outw*outh*bpp bytes from d_out + k*out_stride, read (blend, rows the field does not
+ *              own, the phosphor flags) and written; out_stride >= those bytes, otherwise free.  Base and stride: multiples of 4
+ *              for the 4-byte formats (pixels are stored as dwords and 16-byte runs of dwords), any for RGB / BGR.
+ *   d_out_init, out_init_stride : as d_out / out_stride, READ ONLY (out_init_stride 0 = one shared picture).
+ *   d_state    : n crthip_state, 144 bytes apart, 4-byte aligned; exactly the n records of the call are read and written.
+ *   d_lines    : n * CRT_LINES crthip_line, 32 bytes apart, 4-byte aligned.
+ *   d_recs     : n crthip_knob_rec, 32 bytes apart, 4-byte aligned, READ ONLY.
+ *   d_hist     : n x 32 words (crthip_vhs_bind_history), 4-byte aligned; checked when it is bound.
+ *   d_analog, d_inp, d_inp_flat : n fields crthip_field_stride() bytes apart, 4-byte aligned; ALL crthip_field_stride() bytes of a
+ *              field belong to the library (CRT_INPUT_SIZE samples, the CRTHIP_TAIL mirror, slack the 16-byte pieces of the
+ *              signal kernels run into).  crthip_modulate writes only the samples the reference writes; d_analog is READ ONLY for
+ *              crthip_noise, d_inp for crthip_sync and crthip_decode.
+ * Host pointers (params, env, sched, set_first, passes) follow the C rules for their types.
+ */
+/*
  * One batch of n independent field-passes, everything device resident:
  *   d_images : n images, image k at d_images + k*image_stride (w*h*bpp bytes, or
  *              w*h u16 PPU pixels for NES)
@@ -259,6 +282,7 @@ int  crthip_reserve(crthip_ctx *ctx, int n_fields);
  *              read as well as written when blend != 0, and rows this field does not
  *              own keep their contents (crt_core.c:431,:608,:662)
  *   d_state  : n crthip_state, updated in place
+ * Alignment and extents of all three: BUFFER CONTRACT above (4-byte pixel formats: base and stride multiples of 4; else CRTHIP_E_ARG).
  * Each field starts from a crt_init-clean analog[] (all zero where crt_modulate does
  * not write, crt_ntsc.c:236-238).  Asynchronous on the context's stream: once crthip_reserve
  * has sized the workspace a call allocates nothing and does not synchronise, so the launch
@@ -292,7 +316,7 @@ int  crthip_fieldpass(crthip_ctx *ctx, const crthip_params *p, int n,
  * was captured with, so records written later must stay inside them); env: the same call's bounds, host.
  * Everything crthip_fieldpass accepts is accepted with the same meaning (bloom, FIR, the phosphor flags, both kernel shapes and
  * signal layouts, the overlap chunks, the rand()-noise VHS build), what it refuses is refused, and so are env->magic / env->n that
- * do not match and both phosphor flags at once (CRTHIP_E_ARG; d_out and d_state untouched).  Like crthip_fieldpass after
+ * do not match, d_recs off its 4-byte alignment and both phosphor flags at once (CRTHIP_E_ARG; d_out and d_state untouched).  Like crthip_fieldpass after
  * crthip_reserve it allocates nothing, does not synchronise and can be captured; crthip_fieldpass_signal works after it.
  * Records that do not come from the prepare call that made env (larger noise, larger |saturation|) give unspecified pictures -- but
  * no access outside the buffers: the knobs only enter arithmetic, never an address.
@@ -322,6 +346,7 @@ int  crthip_fieldpass_knobs(crthip_ctx *ctx, const crthip_params *p, int n,
  * blend != 0 (crt_main.c:235) makes the picture a recurrence over the fields: the fields are then decoded in
  * parallel and folded into each other by one small pass per field (needs outh + v_fac >= CRT_LINES).
  * *passes (optional) receives the number of sync fixed-point passes that were needed.
+ * d_images / d_out / d_out_init / d_state: alignment and extents as in the BUFFER CONTRACT (d_out_init is one picture, read only).
  * VHS build: the fields also share ONE rand() stream.  Entry 0 of the bound history array
  * (crthip_vhs_bind_history) is the generator before field 0; a serial pre-pass walks the stream's
  * data-dependent part for all fields (about 0.15 ms per field) and on return entry k is the generator after
@@ -351,7 +376,8 @@ int  crthip_sequence(crthip_ctx *ctx, const crthip_params *p, int n,
  * return entry k is the generator after field k and d_state[k].rn the last value drawn (the incoming .rn is not used); with
  * CRTHIP_F_VHS_DRAW_ABERRATION every field's aberration height is drawn from its own set's stream and left in d_state[k].aux.
  * Again what crthip_sequence gives per set, on the set's slice of the history array as well.
- * Refused (CRTHIP_E_ARG, crthip_error_string says why): anything else in set_first; what crthip_sequence refuses; without
+ * Refused (CRTHIP_E_ARG, crthip_error_string says why): anything else in set_first; what crthip_sequence refuses (the BUFFER
+ * CONTRACT's alignments included: out_init_stride counts like out_stride); without
  * CRTHIP_F_VHS_SET_STREAMS the VHS build with rand() noise (every set would own a rand() stream) and CRTHIP_F_VHS_DRAW_ABERRATION,
  * which draws from that stream (give the aberration heights in d_state[k].aux); with it, no history array bound.
  */
@@ -414,7 +440,7 @@ int  crthip_sequence_sets_knobs(crthip_ctx *ctx, const crthip_params *p,
  *   everything crthip_fieldpass accepts is accepted with the same meaning, per pass (every system, bloom, FIR, formats, kernel
  *   shapes, both signal layouts, CRTHIP_F_NES_SETUP, the phosphor flags: one display step per pass); what it refuses is refused,
  *   and so are n_passes <= 0, n_passes > CRTHIP_STILLS_MAX_PASSES and sched == NULL (CRTHIP_E_ARG, crthip_error_string says why).
- *   A refused call leaves d_out and d_state untouched.
+ *   A refused call leaves d_out and d_state untouched.  Pointers and strides: the BUFFER CONTRACT, as for crthip_fieldpass.
  * What the call adds over the loop:
  *   - noise == 0 (the CLI's test configuration) on the fused LCG-noise path (not the rand()-noise VHS build, not CRTHIP_F_NO_VSYNC,
  *     not an input format crt_modulate refuses): crt_modulate writes the same samples whatever the pass, so the clean signal of
@@ -459,6 +485,7 @@ int  crthip_stills(crthip_ctx *ctx, const crthip_params *p, int n,
  * draw_aberration state[k].aux = the aberration height crt_modulate draws, crt_ntscvhs.c:205-207).  A context whose bound
  * histories (and aux) were filled from that array is told so with crthip_seq_vhs_prechained(ctx, 1); its crthip_seq_encode
  * then accepts any first_index and does not walk the stream again.  (include/crt_hip_node.h does all of this.)
+ * Device pointers of the phases: the BUFFER CONTRACT above, checked by every phase for the arguments it takes.
  */
 int  crthip_vhs_chain(crthip_ctx *ctx, int n, crthip_state *d_state, int draw_aberration);
 int  crthip_seq_vhs_prechained(crthip_ctx *ctx, int on);
@@ -480,7 +507,8 @@ int  crthip_seq_bind_knobs(crthip_ctx *ctx, const crthip_knob_rec *d_recs /* DEV
 /*
  * Stage-level entry points (used by the drop-in layer, which must keep the host's
  * struct CRT coherent between crt_modulate and crt_demodulate, and by the stage
- * parity tests).  d_analog / d_inp hold n fields at crthip_field_stride() spacing.
+ * parity tests).  d_analog / d_inp hold n fields at crthip_field_stride() spacing, 4-byte aligned; d_lines / d_state 4-byte
+ * aligned; d_images / d_out as everywhere (BUFFER CONTRACT above; what it forbids: CRTHIP_E_ARG before any launch).
  */
 /* crt_modulate: writes exactly the samples the reference writes (crt_ntsc.c:205-324),
  * leaving all other samples of d_analog untouched; updates state.ccf (and VHS hsync). */

@@ -811,6 +811,36 @@ static int check_params(crthip_ctx *c, const crthip_params *p, int n)
     return CRTHIP_OK;
 }
 
+/* The buffer contract of include/crt_hip.h ("Buffer contract"; DESIGN.md has the table): the kernels move 4-byte pixels as dwords
+ * and in 16-byte pieces typed to 4-byte alignment (crt_dev.h: gload32 / gstore32, the _nt pieces; crt_encode.hip: k_active_row),
+ * PPU pixels as 16-bit words, and every record array as ints.  A base or a stride off that grid is refused HERE, before anything
+ * is launched, copied or reserved; 3-byte pixels travel bytewise and take any base and stride. */
+static bool off_grid(const void *ptr, size_t stride, size_t a)
+{
+    return a > 1 && ((((size_t) ptr) | stride) & (a - 1)) != 0;
+}
+static int check_images(crthip_ctx *c, const crthip_params *p, const void *d_images, size_t istride)
+{
+    const bool ppu = c->system == CRTHIP_SYSTEM_NES;
+    if (off_grid(d_images, istride, ppu ? 2 : p->in_bpp == 4 ? 4 : 1))
+        return set_err(c, CRTHIP_E_ARG, ppu ? "d_images / image_stride: PPU pixels need 2-byte alignment"
+                                            : "d_images / image_stride: 4-byte pixels need 4-byte alignment", hipSuccess);
+    return CRTHIP_OK;
+}
+static int check_out(crthip_ctx *c, const crthip_params *p, const void *d_out, size_t ostride, const void *d_init = nullptr, size_t init_stride = 0)
+{
+    const size_t a = p->out_bpp == 4 ? 4 : 1;
+    if (off_grid(d_out, ostride, a)) return set_err(c, CRTHIP_E_ARG, "d_out / out_stride: 4-byte pixels need 4-byte alignment", hipSuccess);
+    if (off_grid(d_init, init_stride, a)) return set_err(c, CRTHIP_E_ARG, "d_out_init / out_init_stride: 4-byte pixels need 4-byte alignment", hipSuccess);
+    return CRTHIP_OK;
+}
+/* crthip_state, crthip_line, crthip_knob_rec, the VHS histories; d_analog / d_inp (the signal kernels move dwords too) */
+static int check_word(crthip_ctx *c, const void *ptr, const char *msg)
+{
+    return off_grid(ptr, 0, 4) ? set_err(c, CRTHIP_E_ARG, msg, hipSuccess) : CRTHIP_OK;
+}
+#define CHECK_WORD(c, ptr) check_word(c, ptr, #ptr " needs 4-byte alignment")
+
 /* the stage-level entry points: the host owns the output buffer between the stages (crt_main.c:459-463 fades it itself) */
 static int check_stage_params(crthip_ctx *c, const crthip_params *p, int n)
 {
@@ -845,6 +875,7 @@ int crthip_modulate(crthip_ctx *c, const crthip_params *p, int n, const void *d_
     rc = check_encoder(c, p);
     if (rc) return rc < 0 ? rc : CRTHIP_OK;
     if (!d_images || !d_analog || !d_state) return CRTHIP_E_ARG;
+    if ((rc = check_images(c, p, d_images, istride)) || (rc = CHECK_WORD(c, d_analog)) || (rc = CHECK_WORD(c, d_state))) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     rc = crt_run_encoder_prepare(c, p, false);
     if (rc) return rc;
@@ -860,6 +891,7 @@ int crthip_noise(crthip_ctx *c, const crthip_params *p, int n, const signed char
     if (rc) return rc;
     if (p->out_bpp == 0) return CRTHIP_OK;                       /* crt_core.c:312-315 */
     if (!d_analog || !d_inp || !d_state) return CRTHIP_E_ARG;
+    if ((rc = CHECK_WORD(c, d_analog)) || (rc = CHECK_WORD(c, d_inp)) || (rc = CHECK_WORD(c, d_state))) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     if (p->flags & CRTHIP_F_NO_VSYNC) {                         /* CRT_DO_VSYNC 0: crt_core.c:323-341, before the noise */
         rc = crt_run_clean_vsync(c, n, d_analog, d_state);
@@ -877,6 +909,7 @@ int crthip_sync(crthip_ctx *c, const crthip_params *p, int n, const signed char 
     if (rc) return rc;
     if (p->out_bpp == 0) return CRTHIP_OK;
     if (!d_inp || !d_state || !d_lines) return CRTHIP_E_ARG;
+    if ((rc = CHECK_WORD(c, d_inp)) || (rc = CHECK_WORD(c, d_state)) || (rc = CHECK_WORD(c, d_lines))) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     rc = crt_run_sync(c, p, n, d_inp, d_state, d_lines, 0);
     HIPCHK(c, hipGetLastError());
@@ -890,6 +923,7 @@ int crthip_decode(crthip_ctx *c, const crthip_params *p, int n, const signed cha
     if (rc) return rc;
     if (p->out_bpp == 0) return CRTHIP_OK;
     if (!d_inp || !d_lines || !d_out) return CRTHIP_E_ARG;
+    if ((rc = CHECK_WORD(c, d_inp)) || (rc = CHECK_WORD(c, d_lines)) || (rc = check_out(c, p, d_out, ostride))) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     rc = crt_run_decode(c, p, n, d_inp, d_lines, d_out, ostride);
     HIPCHK(c, hipGetLastError());
@@ -993,6 +1027,7 @@ static int fieldpass_body(crthip_ctx *c, const crthip_params *p, int n, const vo
     int rc = check_params(c, p, n);
     if (rc) return rc;
     if (!d_images || !d_out || !d_state) return CRTHIP_E_ARG;
+    if ((rc = check_images(c, p, d_images, istride)) || (rc = check_out(c, p, d_out, ostride)) || (rc = CHECK_WORD(c, d_state))) return rc;
     if (c->system == CRTHIP_SYSTEM_NTSCVHS && !(p->flags & CRTHIP_F_VHS_LCG_NOISE) && !c->d_vhs_hist)
         return set_err(c, CRTHIP_E_ARG, "VHS: no generator histories bound (crthip_vhs_bind_history)", hipSuccess);
     int enc = check_encoder(c, p);
@@ -1081,6 +1116,7 @@ int crthip_fieldpass(crthip_ctx *c, const crthip_params *p, int n, const void *d
 static int knobs_blob(crthip_ctx *c, const crthip_params *p, int n, const crthip_knob_rec *d_recs, const crthip_knobs_env *env, crthip_params *q)
 {
     if (!d_recs || !env) return CRTHIP_E_ARG;
+    if (CHECK_WORD(c, d_recs)) return CRTHIP_E_ARG;
     if (env->magic != CRTHIP_KNOBS_MAGIC) return set_err(c, CRTHIP_E_ARG, "knobs: env does not come from crthip_knobs_prepare", hipSuccess);
     if (env->n != n) return set_err(c, CRTHIP_E_ARG, "knobs: env was prepared for another number of fields", hipSuccess);
     if ((p->flags & CRTHIP_PHOSPHOR_MASK) == CRTHIP_PHOSPHOR_MASK)
@@ -1161,6 +1197,7 @@ int crthip_stills(crthip_ctx *c, const crthip_params *p, int n, const void *d_im
         return set_err(c, CRTHIP_E_ARG, "crthip_stills: n_passes must be 1 .. CRTHIP_STILLS_MAX_PASSES", hipSuccess);
     if (!sched) return set_err(c, CRTHIP_E_ARG, "crthip_stills: no schedule (sched == NULL)", hipSuccess);
     if (!d_images || !d_out || !d_state) return set_err(c, CRTHIP_E_ARG, "crthip_stills: null device pointer", hipSuccess);
+    if ((rc = check_images(c, p, d_images, istride)) || (rc = check_out(c, p, d_out, ostride)) || (rc = CHECK_WORD(c, d_state))) return rc;
     const bool vhs_rand = c->system == CRTHIP_SYSTEM_NTSCVHS && !(p->flags & CRTHIP_F_VHS_LCG_NOISE);
     if (vhs_rand && !c->d_vhs_hist)
         return set_err(c, CRTHIP_E_ARG, "VHS: no generator histories bound (crthip_vhs_bind_history)", hipSuccess);
@@ -1277,6 +1314,7 @@ int crthip_set_signal_layout(crthip_ctx *c, int padded)
 int crthip_fieldpass_signal(crthip_ctx *c, int n, signed char *d_inp_flat, int *padded)
 {
     if (!c || n <= 0 || !d_inp_flat) return CRTHIP_E_ARG;
+    if (CHECK_WORD(c, d_inp_flat)) return CRTHIP_E_ARG;
     if (n > c->last_n || !c->d_inp) return set_err(c, CRTHIP_E_ARG, "crthip_fieldpass_signal: no field-pass of that many fields went through this context", hipSuccess);
     HIPCHK(c, hipSetDevice(c->device));
     if (padded) *padded = c->last_lay.pitch != c->sd.hres;
@@ -1346,6 +1384,7 @@ static int seq_encode_body(crthip_ctx *c, const crthip_params *p, int n, int fir
     int rc = seq_check(c, p, n);
     if (rc) return rc;
     if (!d_images || !d_state || first_index < 0) return CRTHIP_E_ARG;
+    if ((rc = check_images(c, p, d_images, istride)) || (rc = CHECK_WORD(c, d_state))) return rc;
     const bool vhs = c->system == CRTHIP_SYSTEM_NTSCVHS && !(p->flags & CRTHIP_F_VHS_LCG_NOISE);
     if (vhs && first_index != 0 && !c->vhs_prechained)
         return set_err(c, CRTHIP_E_ARG, "VHS: a video shares ONE rand() stream; its fields cannot start in the middle (first_index != 0)", hipSuccess);
@@ -1397,6 +1436,7 @@ static int seq_sync_body(crthip_ctx *c, const crthip_params *p, int n, crthip_st
     int rc = seq_check(c, p, n);
     if (rc) return rc;
     if (!d_state || n > c->cap_fields) return CRTHIP_E_ARG;
+    if ((rc = CHECK_WORD(c, d_state))) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     SeqScratch sc;
     rc = seq_scratch(c, n, p->outh, &sc);
@@ -1449,6 +1489,7 @@ static int seq_decode_body(crthip_ctx *c, const crthip_params *p, int n, void *d
     int rc = seq_check(c, p, n);
     if (rc) return rc;
     if (!d_out || !d_state || n > c->cap_fields) return CRTHIP_E_ARG;
+    if ((rc = check_out(c, p, d_out, ostride)) || (rc = CHECK_WORD(c, d_state))) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     if (c->system != CRTHIP_SYSTEM_NTSCVHS || (p->flags & CRTHIP_F_VHS_LCG_NOISE)) crt_run_advance_rn(c, n, d_state);
     crthip_params pb = *p;
@@ -1470,6 +1511,7 @@ int crthip_seq_weave(crthip_ctx *c, const crthip_params *p, int n, void *d_out, 
     int rc = seq_check(c, p, n);
     if (rc) return rc;
     if (!d_out || n > c->cap_fields || (p->blend && patch_only)) return CRTHIP_E_ARG;
+    if ((rc = check_out(c, p, d_out, ostride, d_out_init, 0))) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     SeqScratch sc;
     rc = seq_scratch(c, n, p->outh, &sc);
@@ -1517,6 +1559,7 @@ int crthip_seq_weave(crthip_ctx *c, const crthip_params *p, int n, void *d_out, 
 int crthip_vhs_chain(crthip_ctx *c, int n, crthip_state *d_state, int draw_aberration)
 {
     if (!c || n <= 0 || !d_state || c->system != CRTHIP_SYSTEM_NTSCVHS) return CRTHIP_E_ARG;
+    if (CHECK_WORD(c, d_state)) return CRTHIP_E_ARG;
     HIPCHK(c, hipSetDevice(c->device));
     int rc = crt_run_vhs_chain(c, n, d_state, draw_aberration);
     if (rc) return rc;
@@ -1553,6 +1596,7 @@ int crthip_seq_bind_knobs(crthip_ctx *c, const crthip_knob_rec *d_recs, const cr
     if (!c) return CRTHIP_E_ARG;
     if (!d_recs && !env) { c->seq_knob_recs = nullptr; return CRTHIP_OK; }
     if (!d_recs || !env) return set_err(c, CRTHIP_E_ARG, "crthip_seq_bind_knobs: records and env go together ((NULL, NULL) unbinds)", hipSuccess);
+    if (CHECK_WORD(c, d_recs)) return CRTHIP_E_ARG;
     if (env->magic != CRTHIP_KNOBS_MAGIC) return set_err(c, CRTHIP_E_ARG, "knobs: env does not come from crthip_knobs_prepare", hipSuccess);
     if (c->sd.cc_samples == 5)
         return set_err(c, CRTHIP_E_ARG, "knobs: the 5-sample decoder (PV-1000) takes monitor hue and saturation from the uniform parameters", hipSuccess);
@@ -1604,6 +1648,7 @@ static int sequence_body(crthip_ctx *c, const crthip_params *p, int n, const voi
     int rc = check_params(c, p, n);
     if (rc) return rc;
     if (!d_images || !d_out || !d_state) return CRTHIP_E_ARG;
+    if ((rc = check_images(c, p, d_images, istride)) || (rc = check_out(c, p, d_out, ostride, d_out_init, 0)) || (rc = CHECK_WORD(c, d_state))) return rc;
     if (p->out_bpp == 0) return CRTHIP_OK;                /* unknown output format: like crt_demodulate, nothing happens (crt_core.c:312-315) */
     HIPCHK(c, hipSetDevice(c->device));
     crthip_state first;
@@ -1688,6 +1733,7 @@ static int sequence_sets_body(crthip_ctx *c, const crthip_params *p, int n_sets,
     int rc = check_params(c, p, n);
     if (rc) return rc;
     if (!d_images || !d_out || !d_state) return CRTHIP_E_ARG;
+    if ((rc = check_images(c, p, d_images, istride)) || (rc = check_out(c, p, d_out, ostride, d_out_init, out_init_stride)) || (rc = CHECK_WORD(c, d_state)) || (rc = CHECK_WORD(c, d_recs))) return rc;
     if (p->out_bpp == 0) return CRTHIP_OK;                /* as crthip_sequence */
     /* CRTHIP_F_VHS_SET_STREAMS: every set owns one rand() stream (hist[set_first[s]] = its generator before its first field) */
     const bool streams = (p->flags & CRTHIP_F_VHS_SET_STREAMS) != 0;
@@ -1842,6 +1888,7 @@ int crthip_set_overlap(crthip_ctx *c, int chunks)
 int crthip_vhs_bind_history(crthip_ctx *c, unsigned *d_hist)
 {
     if (!c || c->system != CRTHIP_SYSTEM_NTSCVHS) return CRTHIP_E_ARG;
+    if (CHECK_WORD(c, d_hist)) return CRTHIP_E_ARG;
     c->d_vhs_hist = d_hist;
     return CRTHIP_OK;
 }
