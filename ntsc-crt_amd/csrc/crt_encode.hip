@@ -1221,7 +1221,7 @@ static bool encoder_fast_ok(const crthip_params *p)
     const int nz = p->noise < 0 ? -p->noise : p->noise;
     const int ib = p->ire_base < 0 ? -p->ire_base : p->ire_base;
     /* noise * 256 is a 24-bit multiplier in k_active; (y + i + q) * white * 64 + (ire_base << 16) must not wrap: |y + i + q| <= 1020 +
-     * 608 + 533 (8-bit pixels through crt_ntsc.c:307-309, carriers <= 16 / 16), so 2161 * 2^13 * 64 + 2^13 * 2^16 < 2^31.  (Rounds 1-5
+     * 609 + 534 (8-bit pixels through crt_ntsc.c:307-309, carriers <= 16 / 16), so 2163 * 2^13 * 64 + 2^13 * 2^16 < 2^31.  (Rounds 1-5
      * let white up to 2^23 into the fast kernels, where the product could wrap differently from the reference's; nothing sane is near.) */
     bool ok = wh < (1 << 13) && ib < (1 << 13) && nz < (1 << 15);
     if (p->flags & CRTHIP_F_HIPASS) ok = false;                   /* the debug build's high-pass lives in the exact kernels */
