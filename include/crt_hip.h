@@ -323,12 +323,32 @@ int  crthip_fieldpass(crthip_ctx *ctx, const crthip_params *p, int n,
  * REFUSED: CRTHIP_SYSTEM_PV1K.  The 5-sample decoder rotates its carriers by the monitor hue and scales them by the saturation in
  * its own prologue, from crthip_params (crt_core.c:497-505: ((dci * cos + dcq * sin) >> 15) * saturation -- the shift in front of
  * the product keeps the sync kernel from folding either in exactly).
+ *
+ * PICTURE KNOBS: brightness and contrast per field as well -- the other two values the interactive driver turns (the arrow keys,
+ * crt_main.c:317-391) and crt_demodulate reads afresh in every call (crt_core.c:305, 573-575).  crthip_knobs_prepare5 takes
+ * crthip_knobs5 and fills the last three words of every record: bright = brightness - (BLACK_LEVEL + p->black_point) exactly as
+ * crthip_params_finalize derives crthip_params.bright, contrast, and tier_floor = the decoder tier (0, 2 or 3: DESIGN.md 5.3) that
+ * pair asks of the field's lines; env->pic = 1, env->tier_floors = the batch's smallest floor | the largest << 8, env->bright_abs_lo
+ * = the largest |bright| among the fields whose floor is below 2.  p->brightness, p->contrast and p->bright are then ignored too.
+ * It refuses what crthip_knobs_prepare refuses.  All six knob entry points take such records through the arguments they have: the
+ * sync kernel ORs every field's floor into the tier flags of that field's lines -- a field at contrast 40 000 takes the 24-bit
+ * tier, its neighbours stay where they were; a wavefront whose 64 lines straddle two fields decodes once, at the higher tier --
+ * and the decoders read bright and contrast from the record of each line's field (the lane-per-scanline and scanline-parallel
+ * shapes per lane, the wide-run decoder per wavefront: its 16 scanlines are always one field's).  Such a call runs the INTEGER
+ * filter stages (crthip_float_stages_used says 0): the float stages' binade proof is for one |bright|.
+ * Records of crthip_knobs_prepare keep those words and env words 0, and a call with them launches exactly the kernels it
+ * launched before there were picture knobs.  An env whose picture words contradict each other (pic neither 0 nor 1, floors
+ * outside 0..3 or the smallest above the largest, words set without pic) is refused like a wrong magic.  black_point,
+ * white_point and the encoder hue also enter the encoder and stay uniform; CRTHIP_SYSTEM_PV1K stays refused.
  */
 typedef struct crthip_knobs     { int noise, mon_hue, saturation, reserved; } crthip_knobs;                                /* 16 bytes */
-typedef struct crthip_knob_rec  { int noise, huesn, huecs, saturation, bloom_max_e, reserved[3]; } crthip_knob_rec;        /* 32 bytes */
-typedef struct crthip_knobs_env { int magic, n, noise_max, sat_abs_max, loskip_wave_max, reserved[3]; } crthip_knobs_env;
+typedef struct crthip_knobs5    { int noise, mon_hue, saturation, brightness, contrast, reserved[3]; } crthip_knobs5;      /* 32 bytes */
+typedef struct crthip_knob_rec  { int noise, huesn, huecs, saturation, bloom_max_e, bright, contrast, tier_floor; } crthip_knob_rec;   /* 32 bytes */
+typedef struct crthip_knobs_env { int magic, n, noise_max, sat_abs_max, loskip_wave_max, pic, tier_floors, bright_abs_lo; } crthip_knobs_env;
 int  crthip_knobs_prepare(const crthip_params *p, int n, const crthip_knobs *knobs,
                           crthip_knob_rec *recs /* n, host, out */, crthip_knobs_env *env);
+int  crthip_knobs_prepare5(const crthip_params *p, int n, const crthip_knobs5 *knobs,
+                           crthip_knob_rec *recs /* n, host, out */, crthip_knobs_env *env);
 int  crthip_fieldpass_knobs(crthip_ctx *ctx, const crthip_params *p, int n,
                             const void *d_images, size_t image_stride, void *d_out, size_t out_stride,
                             crthip_state *d_state,

@@ -72,16 +72,32 @@ class Knobs(C.Structure):
     _fields_ = [("noise", C.c_int), ("mon_hue", C.c_int), ("saturation", C.c_int), ("reserved", C.c_int)]
 
 
+class Knobs5(C.Structure):
+    """crthip_knobs5 (include/crt_hip.h): the same with the two picture knobs, brightness and contrast."""
+    _fields_ = [("noise", C.c_int), ("mon_hue", C.c_int), ("saturation", C.c_int), ("brightness", C.c_int),
+                ("contrast", C.c_int), ("reserved", C.c_int * 3)]
+
+
 class KnobRec(C.Structure):
-    """crthip_knob_rec (include/crt_hip.h): what the kernels read per field, 32 bytes."""
+    """crthip_knob_rec (include/crt_hip.h): what the kernels read per field, 32 bytes.  ``reserved`` = (bright, contrast,
+    tier_floor): filled by crthip_knobs_prepare5, zeros from crthip_knobs_prepare."""
     _fields_ = [("noise", C.c_int), ("huesn", C.c_int), ("huecs", C.c_int), ("saturation", C.c_int),
                 ("bloom_max_e", C.c_int), ("reserved", C.c_int * 3)]
 
 
+REC_BRIGHT, REC_CONTRAST, REC_TIER_FLOOR = 5, 6, 7      # columns of the (n, 8) record array
+
+
 class KnobsEnv(C.Structure):
-    """crthip_knobs_env (include/crt_hip.h): the batch-wide bounds of one knobs_prepare call."""
+    """crthip_knobs_env (include/crt_hip.h): the batch-wide bounds of one knobs_prepare call.  ``reserved`` = (pic, tier_floors,
+    bright_abs_lo): the picture words of crthip_knobs_prepare5 (zeros from crthip_knobs_prepare), by name below."""
     _fields_ = [("magic", C.c_int), ("n", C.c_int), ("noise_max", C.c_int), ("sat_abs_max", C.c_int),
                 ("loskip_wave_max", C.c_int), ("reserved", C.c_int * 3)]
+
+    pic = property(lambda self: self.reserved[0])                        # the records carry picture knobs
+    tier_floor_min = property(lambda self: self.reserved[1] & 0xff)      # smallest / largest tier floor of the batch
+    tier_floor_max = property(lambda self: (self.reserved[1] >> 8) & 0xff)
+    bright_abs_lo = property(lambda self: self.reserved[2])              # largest |bright| among the fields whose floor is below 2
 
 
 KNOB_REC_INTS = C.sizeof(KnobRec) // 4
@@ -200,6 +216,8 @@ def load_library():
     L.crthip_phosphor_table.argtypes = [ci, C.POINTER(C.c_ubyte)]
     if hasattr(L, "crthip_fieldpass_knobs"):                      # (an earlier build loaded through CRTHIP_LIBDIR for an A/B run has none)
         L.crthip_knobs_prepare.argtypes = [PP, ci, C.POINTER(Knobs), C.POINTER(KnobRec), C.POINTER(KnobsEnv)]
+    if hasattr(L, "crthip_knobs_prepare5"):                       # (likewise)
+        L.crthip_knobs_prepare5.argtypes = [PP, ci, C.POINTER(Knobs5), C.POINTER(KnobRec), C.POINTER(KnobsEnv)]
         L.crthip_fieldpass_knobs.argtypes = [vp, PP, ci, vp, sz, vp, sz, vp, vp, C.POINTER(KnobsEnv)]
     if hasattr(L, "crthip_sequence_knobs"):                       # (likewise)
         L.crthip_sequence_knobs.argtypes = [vp, PP, ci, vp, sz, vp, sz, vp, vp, vp, C.POINTER(KnobsEnv), C.POINTER(ci)]
@@ -242,23 +260,30 @@ def phosphor_table(age):
 
 
 def knobs_prepare(params, knobs):
-    """crthip_knobs_prepare (host only): ``knobs`` = (n, 3) integers, one (noise, mon_hue, saturation) per field, for the
-    finalized ``params`` -> (records as an (n, 8) int32 numpy array in the layout of KnobRec, KnobsEnv)."""
+    """crthip_knobs_prepare / crthip_knobs_prepare5 (host only): ``knobs`` = (n, 3) integers, one (noise, mon_hue, saturation) per
+    field, or (n, 5): (noise, mon_hue, saturation, brightness, contrast) -- the picture knobs as well --, for the finalized
+    ``params`` -> (records as an (n, 8) int32 numpy array in the layout of KnobRec, KnobsEnv).  Every knob entry point of CRT takes
+    either width."""
     import numpy as np
     if hasattr(knobs, "detach"):
         knobs = knobs.detach().cpu().numpy()
     k = np.asarray(knobs)
-    if k.ndim != 2 or k.shape[1] != 3 or k.shape[0] < 1 or not np.issubdtype(k.dtype, np.integer):
-        raise ValueError("knobs must be an (n, 3) integer array of (noise, mon_hue, saturation)")
-    n = int(k.shape[0])
-    kin = np.zeros((n, 4), dtype=np.int32)
-    kin[:, :3] = k
+    if k.ndim != 2 or k.shape[1] not in (3, 5) or k.shape[0] < 1 or not np.issubdtype(k.dtype, np.integer):
+        raise ValueError("knobs must be an (n, 3) integer array of (noise, mon_hue, saturation) "
+                         "or an (n, 5) one of (noise, mon_hue, saturation, brightness, contrast)")
+    n, five = int(k.shape[0]), k.shape[1] == 5
+    kin = np.zeros((n, 8 if five else 4), dtype=np.int32)
+    kin[:, :k.shape[1]] = k
     recs = np.zeros((n, KNOB_REC_INTS), dtype=np.int32)
     env = KnobsEnv()
-    rc = load_library().crthip_knobs_prepare(C.byref(params), n, kin.ctypes.data_as(C.POINTER(Knobs)),
-                                             recs.ctypes.data_as(C.POINTER(KnobRec)), C.byref(env))
+    if five:
+        rc = load_library().crthip_knobs_prepare5(C.byref(params), n, kin.ctypes.data_as(C.POINTER(Knobs5)),
+                                                  recs.ctypes.data_as(C.POINTER(KnobRec)), C.byref(env))
+    else:
+        rc = load_library().crthip_knobs_prepare(C.byref(params), n, kin.ctypes.data_as(C.POINTER(Knobs)),
+                                                 recs.ctypes.data_as(C.POINTER(KnobRec)), C.byref(env))
     if rc:
-        raise ValueError("crthip_knobs_prepare failed (%d)" % rc)
+        raise ValueError("crthip_knobs_prepare%s failed (%d)" % ("5" if five else "", rc))
     return recs, env
 
 
@@ -497,7 +522,8 @@ class CRT:
         return env
 
     def fieldpass_knobs(self, s, knobs, params=None):
-        """fieldpass with per-field (noise, mon_hue, saturation): ``knobs`` = (n, 3) integer array or tensor (None: the records
+        """fieldpass with per-field (noise, mon_hue, saturation): ``knobs`` = (n, 3) integer array or tensor, or (n, 5) with
+        (brightness, contrast) per field as well, which then replace this CRT's own (None: the records
         and bounds of the last upload_knobs -- inside a graph capture, where nothing may be copied from the host).  The batch-
         uniform rest comes from ``params`` (or this CRT's settings); its own noise, mon_hue and saturation are ignored."""
         p = params if params is not None else self.params(s, 0)
@@ -555,7 +581,7 @@ class CRT:
 
     def sequence_knobs(self, s, knobs, out_init=None, params=None):
         """``sequence`` with per-field (noise, mon_hue, saturation): one running television set whose knobs are turned between
-        fields (crt_main.c:351-391).  ``knobs`` = (n, 3) integer array or tensor (None: the records and bounds of the last
+        fields (crt_main.c:351-391).  ``knobs`` = (n, 3) integer array or tensor, or (n, 5): brightness and contrast too (None: the records and bounds of the last
         upload_knobs); the uniform rest comes from ``params`` (or this CRT's settings), whose own noise, mon_hue and saturation
         are ignored.  Returns the number of sync fixed-point passes."""
         p = params if params is not None else self.params(s, 0)
@@ -610,7 +636,7 @@ class CRT:
         return passes.value
 
     def sequence_sets_knobs(self, s, knobs, set_first, out_init=None, params=None, vhs_streams=False):
-        """``sequence_sets`` with per-field (noise, mon_hue, saturation): ``knobs`` = (n, 3), row k = field k of the batch whatever
+        """``sequence_sets`` with per-field (noise, mon_hue, saturation): ``knobs`` = (n, 3) or (n, 5), row k = field k of the batch whatever
         its set (None: the last upload_knobs); equals ``sequence_knobs`` per set on the set's slice of images, state and knobs.
         ``vhs_streams``: as for ``sequence_sets`` (a given ``params`` must carry F_VHS_SET_STREAMS itself)."""
         first, n_sets, init_ptr, init_stride = self._sets_args(set_first, out_init)
@@ -632,7 +658,7 @@ class CRT:
         return passes.value
 
     def seq_bind_knobs(self, knobs, params=None):
-        """Per-field knobs for the phases (seq_encode / seq_sync / seq_decode) of THIS object's n fields: ``knobs`` = (n, 3), row k =
+        """Per-field knobs for the phases (seq_encode / seq_sync / seq_decode) of THIS object's n fields: ``knobs`` = (n, 3) or (n, 5), row k =
         field first_index + k of the video; None unbinds.  ``params``: the blob the records are prepared for (default: this CRT's
         monitor settings -- the records and bounds depend on nothing else).  sequence(), fieldpass() etc. ignore the binding."""
         if knobs is None:

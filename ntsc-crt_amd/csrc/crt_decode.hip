@@ -1,38 +1,18 @@
 /* crt_decode.hip -- host side of the lane-per-scanline decoder (kernel: crt_decode_lane.h).  See crt_dev.h. */
 #include "crt_decode_lane.h"
 
-/* host half of the decoder envelopes: the batch-wide floor of the decoder tier.
- * tier 0 additionally needs the luma coefficients in [2^15, 1.5*2^16) and the chroma ones below 2^15 */
-static int decoder_min_tier(const crthip_ctx *c, const crthip_params *p)
+/* host half of the decoder envelopes: the batch-wide floor of the decoder tier -- what the brightness and the contrast ask
+ * for (crt_setup_decoder_floor, crt_setup.c: the one definition, shared with the per-field floors of crthip_knobs_prepare5), raised by
+ * the context's switches.  A call with picture knobs starts from the smallest floor among its fields instead: the sync kernel has
+ * ORed every field's own floor into its lines' tier flags. */
+int crt_decoder_min_tier(const crthip_ctx *c, const crthip_params *p)
 {
-    const int b = p->bright < 0 ? -p->bright : p->bright;
-    const long ct = p->contrast < 0 ? -(long) p->contrast : (long) p->contrast;
-    if (c->force_exact || b > FAST_BRIGHT_MAX || ct >= (1 << 23)) return 3;
-    /* the 64-bit-mad tiers: luma coefficients near 2^16 (the form x' = hi32(((c - 2^16) << 16) * d + {2^31, u})), chroma ones
-     * below 2^15 */
-    bool coef_ok = p->eq_lf[0] >= 32768 && p->eq_lf[0] < 98304 && p->eq_hf[0] >= 32768 && p->eq_hf[0] < 98304 &&
-                   p->eq_lf[1] > 0 && p->eq_lf[1] < 32768 && p->eq_hf[1] > 0 && p->eq_hf[1] < 32768 &&
-                   p->eq_lf[2] > 0 && p->eq_lf[2] < 32768 && p->eq_hf[2] > 0 && p->eq_hf[2] < 32768;
-    /* ... and no luma stage may wrap in the reference: stage k of a cascade with alpha = c / 2^16 obeys
-     * |x_k| <= (alpha |x_(k-1)| + 1) / (1 - |1 - alpha|), its product is c * (x_(k-1) - x_k) */
-    for (int cas = 0; cas < 2 && coef_ok; cas++) {
-        const double cf = cas ? p->eq_hf[0] : p->eq_lf[0], al = cf / 65536.0, den = 1.0 - (al > 1.0 ? al - 1.0 : 1.0 - al);
-        double prev = 127.0 + b, worst = 0.0;
-        for (int k = 0; k < 4; k++) {
-            const double cur = (al * prev + 1.0) / den + 1.0;
-            if (prev + cur > worst) worst = prev + cur;
-            prev = cur;
-        }
-        if (cf * worst + 32768.0 >= 2147483647.0) coef_ok = false;
-    }
-    if (c->no_tier0 || !coef_ok || b > T0_BRIGHT_MAX) return 2;
-    /* ... and ((v >> 12) * contrast) >> 8 must not wrap in the reference, because tiers 0 / 1 take it from an exact 64-bit
-     * product (D9): |luma| <= 10 U + 64 with U = 127 + |bright| (both luma gain sets), |chroma| <= 3870,
-     * |v| <= 4 * 4095 * |luma| + (4530 + 7021) * |chroma| */
-    const long vmax = 16380L * (10L * (127 + b) + 64) + 11551L * 3870L;
-    if (((vmax >> 12) + 1) * ct >= (1L << 31)) return 2;
-    return c->no_loskip ? 2 : 0;                /* crthip_set_exact(3): keep the I/Q low cascades = the 24-bit tier */
+    const int fl = knob_pic_call(c) ? c->knob_floor_lo : crt_setup_decoder_floor(p, p->bright, p->contrast);
+    if (c->force_exact || fl >= 3) return 3;
+    if (c->no_tier0 || c->no_loskip) return 2;  /* crthip_set_exact(2) / (3): keep the I/Q low cascades = the 24-bit tier */
+    return fl;
 }
+static int decoder_min_tier(const crthip_ctx *c, const crthip_params *p) { return crt_decoder_min_tier(c, p); }
 
 /* Float filter stages for tier group 0 (crt_decode_lane.h, eq_stepf_yiq)?  Yes where the switch is on (CRTHIP_DEC_FLOAT, default),
  * the system has 4 samples per chroma cycle (the PV-1000's 1 487-sample lines stay on the integer stages) and the host's proof holds
@@ -42,7 +22,8 @@ bool crt_decode_fstages(crthip_ctx *c, const crthip_params *p, int min_tier, FSt
 {
     memset(fs, 0, sizeof *fs);
     c->last_fstage = 0;
-    if (!c->dec_float || min_tier > 1) return false;
+    /* picture knobs: the integer stages (the binade proof below is for ONE |bright|) */
+    if (!c->dec_float || min_tier > 1 || knob_pic_call(c)) return false;
     crthip_fstages q;
     if (crthip_float_stages_query(p, 0, &q) != 1) return false;
     for (int k = 0; k < 4; k++) {
@@ -94,6 +75,8 @@ int crt_run_decode(crthip_ctx *c, const crthip_params *p, int n, const signed ch
     const bool rows_shape = !p->eq_kernel && (c->shape == 2 || (c->shape == 0 && n <= ROWS_SHAPE_MAX_FIELDS &&
                             !(n >= WIDE_SHAPE_MIN_FIELDS && !p->bloom && crt_decode_wide_ok(c, p, decoder_min_tier(c, p), wide_px))));
     if (rows_shape) return crt_run_decode_rows(c, p, n, d_inp, d_lines, d_out, ostride, fstride);
+    /* picture knobs on the lane-per-scanline shape: the PK instantiations of k_decode (crt_decode_pk.hip; the bloom build's: crt_decode3.hip) */
+    if (knob_pic_call(c) && !p->bloom) return crt_run_decode_pk(c, p, n, d_inp, d_lines, d_out, ostride, fstride, wide_px);
     if (p->bloom) return crt_run_decode_bloom_lanes(c, p, n, d_inp, d_lines, d_out, ostride, decoder_min_tier(c, p), fstride);
     /* FIR build: the filters only add, their outputs stay inside the hull of the inputs, so the 24-bit envelope
      * of tier 2 carries over (tier 4); beyond it the exact instantiation (tier 5) */

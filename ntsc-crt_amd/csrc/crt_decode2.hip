@@ -25,7 +25,9 @@
 
 #define DPP_ROW_SHR4 0x114
 
-template <class S, bool NARROW, bool BPP3, int TS_>
+/* PK (picture knobs, crthip_knobs_prepare5): brightness and contrast of a scanline from the crthip_knob_rec of its field (the record
+ * pointer travels in the blob, knob_blob_recs): every lane of the scanline's DPP rows loads its own copy once, beside lines[gl] */
+template <class S, bool NARROW, bool BPP3, int TS_, bool PK = false>
 __global__ void __launch_bounds__(64)
 k_decode_row(const crthip_params P, int n_fields, const signed char *__restrict__ inp, size_t fstride,
              const crthip_line *__restrict__ lines, unsigned char *__restrict__ outp, size_t ostride,
@@ -125,7 +127,12 @@ k_decode_row(const crthip_params P, int n_fields, const signed char *__restrict_
     const unsigned long long slot_mask = LPL == 32 ? 0xffffffffull : 0xffffull;
     int pxn = 0;                                         /* next pixel of my scanline (the same in all its lanes) */
 
-    const int bright = P.bright, contrast = P.contrast;
+    int bright = P.bright, contrast = P.contrast;
+    if constexpr (PK) {
+        static_assert(!PK || CCS == 4, "picture knobs: the 4-sample systems");
+        const crthip_knob_rec *kr = knob_blob_recs(P) + f;
+        bright = kr->bright; contrast = kr->contrast;
+    }
     const unsigned psel = P.out_format == CRTHIP_FMT_BGRA ? 0x03020100u : P.out_format == CRTHIP_FMT_RGBA ? 0x03000102u
                         : P.out_format == CRTHIP_FMT_ARGB ? 0x00010203u : 0x02010003u /* ABGR */;
     const unsigned usel = P.out_format == CRTHIP_FMT_BGRA ? 0x03020100u : P.out_format == CRTHIP_FMT_RGBA ? 0x03000102u
@@ -299,7 +306,11 @@ int crt_run_decode_rows(crthip_ctx *c, const crthip_params *p, int n, const sign
         ProfScope ps(c, CRTHIP_K_DECODE);
         for (int rank = 0; rank < passes; rank++) {
 #define CRTHIP_LAUNCH_ROWS_T(B3, TSV) \
-    do { if (narrow_ok) hipLaunchKernelGGL((k_decode_row<S, true, B3, TSV>), dim3((total + 3) / 4), dim3(64), 0, c->stream, *p, n, d_inp, fstride, d_lines, o, ostride, rank, 0); \
+    do { if constexpr (S::CCS == 4) { if (knob_pic_call(c)) { /* picture knobs: bright / contrast per scanline */ \
+             if (narrow_ok) hipLaunchKernelGGL((k_decode_row<S, true, B3, TSV, true>), dim3((total + 3) / 4), dim3(64), 0, c->stream, *p, n, d_inp, fstride, d_lines, o, ostride, rank, 0); \
+             hipLaunchKernelGGL((k_decode_row<S, false, B3, TSV, true>), dim3((total + 1) / 2), dim3(64), 0, c->stream, *p, n, d_inp, fstride, d_lines, o, ostride, rank, narrow_ok ? 0 : 1); \
+             break; } } \
+         if (narrow_ok) hipLaunchKernelGGL((k_decode_row<S, true, B3, TSV>), dim3((total + 3) / 4), dim3(64), 0, c->stream, *p, n, d_inp, fstride, d_lines, o, ostride, rank, 0); \
          hipLaunchKernelGGL((k_decode_row<S, false, B3, TSV>), dim3((total + 1) / 2), dim3(64), 0, c->stream, *p, n, d_inp, fstride, d_lines, o, ostride, rank, narrow_ok ? 0 : 1); } while (0)
             /* tile of 16 samples: 9 KB of LDS per wave instead of 14 (4 waves per SIMD instead of 2.75) but twice the
              * per-tile overheads: better once the launch has a few waves per SIMD (measured: batch 64

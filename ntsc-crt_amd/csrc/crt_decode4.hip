@@ -53,7 +53,11 @@ __device__ __forceinline__ long mad64_vv(int d, int m, long acc)
  * but makes twice as many waves, each half as long: a batch of 64 fields of 1920x1080 is 960 waves of 16 scanlines on 1024 SIMDs --
  * less than one wave per SIMD, each walking its 16 x 1920 pixels alone -- and 1920 waves of 8 (VERDICT round 4, item 3b;
  * profiles/r05_experiments.txt section 6). */
-template <class S, int LPW>
+/* PK (picture knobs, crthip_knobs_prepare5): a wave's LPW scanlines are always ONE field's (LINES % LPW == 0, asserted below), so its
+ * field's brightness and contrast are wave-uniform: one load per wave from the field's crthip_knob_rec (knob_blob_recs), and the
+ * pixel stage's contrast stays the scalar operand it is.  (The TIER of the wave is still decided over its 64-scanline group, which
+ * may straddle two fields: the higher floor wins, as in k_decode.) */
+template <class S, int LPW, bool PK = false>
 __global__ void __launch_bounds__(64)
 k_decode_wide(const crthip_params P, int n_fields, const signed char *__restrict__ inp, size_t fstride,
               const crthip_line *__restrict__ lines, unsigned char *__restrict__ outp, size_t ostride, int min_tier,
@@ -123,7 +127,13 @@ k_decode_wide(const crthip_params P, int n_fields, const signed char *__restrict
     wk[1] = c < 2 ? 65536 : c == 2 ? w1 : w0;
     wk[2] = c < 2 ? 65536 : c == 2 ? -w0 : w1;
     wk[3] = c < 2 ? 65536 : c == 2 ? -w1 : -w0;
-    const int bl = c < 2 ? P.bright : 0;
+    int bright_w = P.bright, contrast_w = P.contrast;
+    if constexpr (PK) {
+        const crthip_knob_rec *kr = knob_blob_recs(P) + (bid * LPW) / S::LINES;
+        bright_w = __builtin_amdgcn_readfirstlane(kr->bright);
+        contrast_w = __builtin_amdgcn_readfirstlane(kr->contrast);
+    }
+    const int bl = c < 2 ? bright_w : 0;
     const bool near1 = c < 2;
     const int M = c == 0 ? (P.eq_lf[0] - 65536) * 65536 : c == 1 ? (P.eq_hf[0] - 65536) * 65536 : c == 2 ? P.eq_hf[1] * 65536 : P.eq_hf[2] * 65536;
     const int g2 = c == 1 ? 9175 : c == 2 ? 1311 : 0;          /* crt_core.c:272-286 (the host refuses other gains) */
@@ -136,7 +146,7 @@ k_decode_wide(const crthip_params P, int n_fields, const signed char *__restrict
     int h0 = 0, h1 = 0, h2 = 0;                                /* my input history (top band, crt_core.c:229-231) */
 
     const unsigned dx = (unsigned) P.dx;
-    const int contrast12 = P.contrast * 4096;
+    const int contrast12 = contrast_w * 4096;
     long alpha_pair = (long) 0xff00ul << 32;
     asm volatile("" : "+v"(alpha_pair));
     const unsigned psel = pack_selector(P.out_format);
@@ -288,7 +298,14 @@ int crt_run_decode_wide(crthip_ctx *c, const crthip_params *p, int n, const sign
             const int nblk = (total + lpw - 1) / lpw;
             const block_order bo = make_block_order(nblk, c->wide_order_env == 0 || c->wide_order_env == -1 ? n : c->wide_order_env);
             const dim3 ogrid(bo.grid);
-            if (lpw == 8)
+            if (knob_pic_call(c)) {                         /* picture knobs: bright / contrast of the wave's field */
+                if (lpw == 8)
+                    hipLaunchKernelGGL((k_decode_wide<S, 8, true>), ogrid, block, 0, c->stream, *p, n, d_inp, fstride, d_lines, (unsigned char *) d_out, ostride,
+                                       min_tier, rank, n_px, ppos_end, bo.K, bo.per);
+                else
+                    hipLaunchKernelGGL((k_decode_wide<S, 16, true>), ogrid, block, 0, c->stream, *p, n, d_inp, fstride, d_lines, (unsigned char *) d_out, ostride,
+                                       min_tier, rank, n_px, ppos_end, bo.K, bo.per);
+            } else if (lpw == 8)
                 hipLaunchKernelGGL((k_decode_wide<S, 8>), ogrid, block, 0, c->stream, *p, n, d_inp, fstride, d_lines, (unsigned char *) d_out, ostride,
                                    min_tier, rank, n_px, ppos_end, bo.K, bo.per);
             else

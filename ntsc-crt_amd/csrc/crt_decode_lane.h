@@ -317,13 +317,43 @@ __device__ __forceinline__ unsigned unpack_selector(int format)
 /* FSTAGE (tier group 0 of the 4-sample systems only): the filter stages of tiers 0 and 1 as float sub + fma (eq_stepf_yiq), with
  * the carrier products (s * wave) >> 9 as one fma each -- exact for every carrier of tier 1, so the two tiers are one loop there.
  * FS: the host's constants (crthip_float_stages_query); launched only where its verdict is yes. */
-template <class S, int TG, bool BPP3, int PXT, bool BLOOM = false, bool FSTAGE = false>
+/* PK (picture knobs, crthip_knobs_prepare5; instantiated by crt_decode_pk.hip): brightness and contrast of every scanline come from
+ * the crthip_knob_rec of ITS field -- a wave's 64 scanlines straddle field boundaries, so both are per-lane registers, loaded once in
+ * front of the sample loop beside lines[gid]; the luma input s + bright becomes a vector add and contrast << 12 a vector operand
+ * of the 64-bit multiply-adds.  The record pointer travels in the blob (knob_blob_recs).  Integer stages only. */
+template <bool PK> __device__ __forceinline__ int pk_bright(const crthip_params &P, int f)
+{
+    if constexpr (PK) return knob_blob_recs(P)[f].bright; else return P.bright;
+}
+template <bool PK> __device__ __forceinline__ int pk_contrast(const crthip_params &P, int f)
+{
+    if constexpr (PK) return knob_blob_recs(P)[f].contrast; else return P.contrast;
+}
+/* mad64_vs / mad64_vs0 (crt_dev.h) with the multiplier wave-uniform (PK false: the same instruction as there) or per lane */
+template <bool PK> __device__ __forceinline__ long mad64_pk(int d, int m, long acc)
+{
+    if constexpr (PK) {
+        long r, carry;
+        asm("v_mad_i64_i32 %0, %1, %2, %3, %4" : "=v"(r), "=s"(carry) : "v"(d), "v"(m), "v"(acc));
+        return r;
+    } else return mad64_vs(d, m, acc);
+}
+template <bool PK> __device__ __forceinline__ long mad64_pk0(int d, int m)
+{
+    if constexpr (PK) {
+        long r, carry;
+        asm("v_mad_i64_i32 %0, %1, %2, %3, 0" : "=v"(r), "=s"(carry) : "v"(d), "v"(m));
+        return r;
+    } else return mad64_vs0(d, m);
+}
+template <class S, int TG, bool BPP3, int PXT, bool BLOOM = false, bool FSTAGE = false, bool PK = false>
 __global__ void __launch_bounds__(64) DEC_OCCUPANCY_ATTR
 k_decode(const crthip_params P, int n_fields, const signed char *__restrict__ inp, size_t fstride,
          const crthip_line *__restrict__ lines, unsigned char *__restrict__ outp, size_t ostride, int min_tier,
          int want_rank, const int *__restrict__ perm, int order_k, int order_per, const FStageArgs FS)
 {
     static_assert(!FSTAGE || (TG == 0 && S::CCS == 4), "float stages: tiers 0 / 1 of the 4-sample systems");
+    static_assert(!PK || (!FSTAGE && S::CCS == 4), "picture knobs: the integer stages of the 4-sample systems");
     constexpr int TLO = 2 * TG;
     constexpr int IN_TILE_DW = DEC_IN_TILE_DW, IN_PIECES = IN_TILE_DW / 4;
     using TIN = TileRows<IN_TILE_DW>;                 /* row addressing of both tiles: conflict-free lane-per-row AND cooperatively (crt_dev.h) */
@@ -404,7 +434,7 @@ k_decode(const crthip_params P, int n_fields, const signed char *__restrict__ in
     int ph5 = (xq0 * 4) % 5;                       /* sample index % 5 */
     /* luma band gains of the build, crt_core.c:272-286 */
     constexpr int GY1 = S::CCS == 5 ? 12192 : 8192, GY2 = S::CCS == 5 ? 7775 : 9175;
-    const int bright = P.bright, contrast = P.contrast;
+    const int bright = pk_bright<PK>(P, f), contrast = pk_contrast<PK>(P, f);
     const int ylf = P.eq_lf[0], yhf = P.eq_hf[0], ilf = P.eq_lf[1], ihf = P.eq_hf[1], qlf = P.eq_lf[2], qhf = P.eq_hf[2];
     const unsigned psel = pack_selector(P.out_format), usel = unpack_selector(P.out_format);
     const bool rgb_order = P.out_format == CRTHIP_FMT_RGB;
@@ -554,9 +584,9 @@ k_decode(const crthip_params P, int n_fields, const signed char *__restrict__ in
                          * shift, multiply, shift.  The 64-bit product is exact where the reference's 32-bit one wraps: equal
                          * inside the envelope (|v| < 2^27.3, |contrast| <= 32768, host-checked).  The red row carries the
                          * opaque alpha along: + 0xff00 through the addend, clamped to [0xff00, 0xffff]. */
-                        int r = pair_hi(mad64_vs(vr & ~0xfff, contrast12, alpha_pair));
-                        int g = pair_hi(mad64_vs0(vg & ~0xfff, contrast12));
-                        int b = pair_hi(mad64_vs0(vb & ~0xfff, contrast12));
+                        int r = pair_hi(mad64_pk<PK>(vr & ~0xfff, contrast12, alpha_pair));
+                        int g = pair_hi(mad64_pk0<PK>(vg & ~0xfff, contrast12));
+                        int b = pair_hi(mad64_pk0<PK>(vb & ~0xfff, contrast12));
                         r = clampi(r, 0xff00, 0xffff); g = clampi(g, 0, 255); b = clampi(b, 0, 255);
                         rgb = lshl_or(lshl_or((unsigned) r, 8, (unsigned) g), 8, (unsigned) b);       /* 0xffRRGGBB */
                     } else {

@@ -213,9 +213,8 @@ template <class S> __device__ __forceinline__ int sig_phys(int flat)
 #define LOSKIP_WAVE_MAX   65532           /* |wave[k]| bound of decoder tier 0's products: (wave << 7) fits 24 bits; also the
                                              no-low-cascade bound for arbitrary inp[] (|s * wave >> 9| <= 16383) */
 #define T0_WAVE_MAX       120000          /* |wave[k]| bound of decoder tiers 0 and 1 */
-#define T0_BRIGHT_MAX     2600            /* |bright| bound of decoder tiers 0 and 1  */
 #define FAST_WAVE_MAX     524288          /* |wave[k]| bound of the fast decoder, 2^19 */
-#define FAST_BRIGHT_MAX   130000          /* |bright| bound of the fast decoder        */
+/* (T0_BRIGHT_MAX, FAST_BRIGHT_MAX: crt_setup.h, beside crt_setup_decoder_floor, which the host's C89 half shares) */
 #define LCG_MUL 214019u          /* crt_core.c:359 */
 #define LCG_ADD 140327895u
 
@@ -444,6 +443,15 @@ __device__ __forceinline__ const crthip_knob_rec *knob_blob_recs(const crthip_pa
     return (const crthip_knob_rec *) (((unsigned long long) (unsigned) P.reserved[1] << 32) | (unsigned) P.reserved[0]);
 }
 
+/* Picture knobs (crthip_knobs_prepare5): is a call with such records under way?  The decoders then launch their PK instantiations */
+static inline bool knob_pic_call(const crthip_ctx *c);
+/* the tier flags a field's floor (crthip_knob_rec.tier_floor: 0, 2 or 3) puts on each of its lines -- what the decoders (and, min_tier >= 4,
+ * their FIR tiers) read as "24-bit tier" / "exact tier" */
+__device__ __forceinline__ int tier_floor_flags(int tier_floor)
+{
+    return tier_floor >= 3 ? CRTHIP_LINE_EXACT : tier_floor >= 2 ? CRTHIP_LINE_NOT64 : 0;
+}
+
 /* fields per launch up to which the scanline-parallel kernel shapes are chosen automatically: lane-per-scanline needs
  * n * 240 / 64 wavefronts >= a few per SIMD (1024 SIMDs) to hide its serial chains.  Measured crossovers
  * (profiles/r02_shape_sweep.txt): decoders between 128 and 256 fields, encoders between 256 and 512 (a field-pass of
@@ -599,6 +607,9 @@ struct crthip_ctx {
     int overlap_chunks;         /* crthip_fieldpass: chunks alternating between two streams (1 = off) */
     const crthip_knob_rec *knob_recs;   /* a *_knobs call (or a phase with bound records) under way: the caller's device records (field 0 of the call), else nullptr */
     int knob_loskip;            /* ... and its crthip_knobs_env.loskip_wave_max */
+    int knob_pic;               /* ... its records carry picture knobs (crthip_knobs_prepare5): the sync kernel ORs every field's tier floor into its
+                                   lines' flags, the decoders' PK instantiations read bright / contrast from the record of each line's field */
+    int knob_floor_lo;          /* ... and the smallest tier floor of its fields: what decoder_min_tier starts from then */
     const crthip_knob_rec *seq_knob_recs;   /* crthip_seq_bind_knobs: the shard's records for crthip_seq_encode / _sync / _decode (nullptr: none bound) */
     crthip_knobs_env seq_knob_env;          /* ... and the library's copy of their bounds */
     hipStream_t aux_stream;
@@ -612,6 +623,8 @@ struct crthip_ctx {
     int npend, cappend;
     char err[256];
 };
+
+static inline bool knob_pic_call(const crthip_ctx *c) { return c->knob_recs != nullptr && c->knob_pic != 0; }
 
 static inline int set_err(crthip_ctx *c, int code, const char *what, hipError_t e)
 {
@@ -728,6 +741,10 @@ int crt_run_sync(crthip_ctx *c, const crthip_params *p, int n, const signed char
                  crthip_line *d_lines, int advance_rn, int preset_ccf = 0, const sig_layout *lay = nullptr);
 int crt_run_decode(crthip_ctx *c, const crthip_params *p, int n, const signed char *d_inp,
                    const crthip_line *d_lines, void *d_out, size_t ostride, size_t fstride = 0);   /* fstride 0: the flat layout's */
+int crt_decoder_min_tier(const crthip_ctx *c, const crthip_params *p);                             /* crt_decode.hip */
+/* crt_run_decode's lane-per-scanline launches for a call with picture knobs (crt_decode_pk.hip); p went through crt_decode_check */
+int crt_run_decode_pk(crthip_ctx *c, const crthip_params *p, int n, const signed char *d_inp, const crthip_line *d_lines,
+                      void *d_out, size_t ostride, size_t fstride, bool wide);
 int crt_decode_check(crthip_ctx *c, const crthip_params *p);
 bool crt_decode_wide_ok(const crthip_ctx *c, const crthip_params *p, int min_tier, bool wide);
 bool crt_decode_fstages(crthip_ctx *c, const crthip_params *p, int min_tier, FStageArgs *fs);   /* crt_decode.hip */

@@ -1113,6 +1113,15 @@ int crthip_fieldpass(crthip_ctx *c, const crthip_params *p, int n, const void *d
  * record of the call's field 0 (knob_blob_set) for the KN kernels -- mon_hue / huesn / huecs / bloom_max_e are read by them alone,
  * from the records -- and c->knob_loskip = the sync chain's no-low-cascade bound.  The caller sets c->knob_recs for the duration of
  * its launches and clears it on every way out. */
+/* the picture words of an env (crthip_knobs_prepare5; all 0 from crthip_knobs_prepare): do they agree with each other? */
+static bool knobs_env_pic_ok(const crthip_knobs_env *env)
+{
+    if (env->pic == 0) return env->tier_floors == 0 && env->bright_abs_lo == 0;
+    const int lo = env->tier_floors & 0xff, hi = (env->tier_floors >> 8) & 0xff;
+    return env->pic == 1 && (env->tier_floors & ~0xffff) == 0 && lo <= hi && hi <= 3 && lo != 1 && hi != 1 &&
+           env->bright_abs_lo >= 0 && env->bright_abs_lo <= T0_BRIGHT_MAX && (lo < 2 || env->bright_abs_lo == 0);
+}
+
 static int knobs_blob(crthip_ctx *c, const crthip_params *p, int n, const crthip_knob_rec *d_recs, const crthip_knobs_env *env, crthip_params *q)
 {
     if (!d_recs || !env) return CRTHIP_E_ARG;
@@ -1124,6 +1133,9 @@ static int knobs_blob(crthip_ctx *c, const crthip_params *p, int n, const crthip
     if (c->sd.cc_samples == 5)
         return set_err(c, CRTHIP_E_ARG, "knobs: the 5-sample decoder (PV-1000) takes monitor hue and saturation from the uniform parameters", hipSuccess);
     if (env->noise_max < 0 || env->sat_abs_max < 0) return set_err(c, CRTHIP_E_ARG, "knobs: env bounds", hipSuccess);
+    if (!knobs_env_pic_ok(env)) return set_err(c, CRTHIP_E_ARG, "knobs: the env's picture words contradict each other (not from crthip_knobs_prepare5)", hipSuccess);
+    c->knob_pic = env->pic;
+    c->knob_floor_lo = env->pic ? (env->tier_floors & 0xff) : 0;
     *q = *p;
     q->noise = env->noise_max;
     q->saturation = env->sat_abs_max;
@@ -1601,6 +1613,7 @@ int crthip_seq_bind_knobs(crthip_ctx *c, const crthip_knob_rec *d_recs, const cr
     if (c->sd.cc_samples == 5)
         return set_err(c, CRTHIP_E_ARG, "knobs: the 5-sample decoder (PV-1000) takes monitor hue and saturation from the uniform parameters", hipSuccess);
     if (env->n <= 0 || env->noise_max < 0 || env->sat_abs_max < 0) return set_err(c, CRTHIP_E_ARG, "knobs: env bounds", hipSuccess);
+    if (!knobs_env_pic_ok(env)) return set_err(c, CRTHIP_E_ARG, "knobs: the env's picture words contradict each other (not from crthip_knobs_prepare5)", hipSuccess);
     c->seq_knob_recs = d_recs;
     c->seq_knob_env = *env;
     return CRTHIP_OK;

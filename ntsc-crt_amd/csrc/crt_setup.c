@@ -705,37 +705,52 @@ abs_sat(int v)
  * from the uniform noise and saturation.  The signal range grows with the noise on either side of zero, so the no-low-cascade
  * bound of the batch is the smaller of the bounds at the smallest and the largest noise.
  */
-int
-crthip_knobs_prepare(const crthip_params *p, int n, const crthip_knobs *knobs, crthip_knob_rec *recs, crthip_knobs_env *env)
+/* kn: the caller's knobs as ints, `stride` apart: noise, mon_hue, saturation and -- pic: crthip_knobs5 -- brightness, contrast */
+static int
+knobs_prepare_any(const crthip_params *p, int n, const int *kn, int stride, int pic, crthip_knob_rec *recs, crthip_knobs_env *env)
 {
     struct crt_sysdef d;
     crthip_params q;
     int k, sn, cs, lo, hi, bound, b2;
     int noise_lo, noise_hi, noise_abs = 0, sat_abs = 0;
+    int floor_lo = 3, floor_hi = 0, bright_abs = 0;
 
-    if (p == 0 || knobs == 0 || recs == 0 || env == 0 || n <= 0 || p->finalized != CRTHIP_PARAMS_MAGIC ||
+    if (p == 0 || kn == 0 || recs == 0 || env == 0 || n <= 0 || p->finalized != CRTHIP_PARAMS_MAGIC ||
         crt_sysdef_get(&d, p->system, p->chroma_pattern) != CRTHIP_OK) {
         return CRTHIP_E_ARG;
     }
     memset(env, 0, sizeof(*env));
-    noise_lo = noise_hi = knobs[0].noise;
+    noise_lo = noise_hi = kn[0];
     for (k = 0; k < n; k++) {
-        const int noise = knobs[k].noise;
+        const int *const kk = kn + (size_t) k * (size_t) stride;
+        const int noise = kk[0];
         const int max_e = (128 + (noise / 2)) * d.av_len;           /* crt_core.c:400 */
         if (p->bloom && (max_e <= 0 || noise < 0)) {
             return CRTHIP_E_ARG;                                    /* as crthip_params_finalize */
         }
         memset(&recs[k], 0, sizeof(recs[k]));
-        crt_setup_sincos14(&sn, &cs, ((knobs[k].mon_hue % 360) + 33) * 8192 / 180);      /* crt_core.c:318-320 */
+        crt_setup_sincos14(&sn, &cs, ((kk[1] % 360) + 33) * 8192 / 180);                 /* crt_core.c:318-320 */
         recs[k].noise = noise;
         recs[k].huesn = sn >> 11;
         recs[k].huecs = cs >> 11;
-        recs[k].saturation = knobs[k].saturation;
+        recs[k].saturation = kk[2];
         recs[k].bloom_max_e = max_e;
+        if (pic) {
+            /* the decoder's two: the luma offset as crthip_params_finalize derives it (crt_core.c:305), the contrast as it is, and
+             * the tier they ask of the field's lines (k_hsync_wave turns it into the lines' tier flags) */
+            const int bright = kk[3] - (d.black_level + p->black_point);
+            const int fl = crt_setup_decoder_floor(p, bright, kk[4]);
+            recs[k].bright = bright;
+            recs[k].contrast = kk[4];
+            recs[k].tier_floor = fl;
+            if (fl < floor_lo) floor_lo = fl;
+            if (fl > floor_hi) floor_hi = fl;
+            if (fl < 2 && abs_sat(bright) > bright_abs) bright_abs = abs_sat(bright);
+        }
         if (noise < noise_lo) noise_lo = noise;
         if (noise > noise_hi) noise_hi = noise;
         if (abs_sat(noise) > noise_abs) noise_abs = abs_sat(noise);
-        if (abs_sat(knobs[k].saturation) > sat_abs) sat_abs = abs_sat(knobs[k].saturation);
+        if (abs_sat(kk[2]) > sat_abs) sat_abs = abs_sat(kk[2]);
     }
     q = *p;
     q.noise = noise_lo;
@@ -749,7 +764,73 @@ crthip_knobs_prepare(const crthip_params *p, int n, const crthip_knobs *knobs, c
     env->noise_max = noise_abs;
     env->sat_abs_max = sat_abs;
     env->loskip_wave_max = b2 < bound ? b2 : bound;
+    if (pic) {
+        env->pic = 1;
+        env->tier_floors = floor_lo | (floor_hi << 8);
+        env->bright_abs_lo = bright_abs;
+    }
     return CRTHIP_OK;
+}
+
+int
+crthip_knobs_prepare(const crthip_params *p, int n, const crthip_knobs *knobs, crthip_knob_rec *recs, crthip_knobs_env *env)
+{
+    return knobs_prepare_any(p, n, knobs ? &knobs->noise : 0, (int) (sizeof(*knobs) / sizeof(int)), 0, recs, env);
+}
+
+/* The same with brightness and contrast per field: the records' last three words and the env's picture words filled in. */
+int
+crthip_knobs_prepare5(const crthip_params *p, int n, const crthip_knobs5 *knobs, crthip_knob_rec *recs, crthip_knobs_env *env)
+{
+    return knobs_prepare_any(p, n, knobs ? &knobs->noise : 0, (int) (sizeof(*knobs) / sizeof(int)), 1, recs, env);
+}
+
+/*
+ * Host half of the decoder envelopes: the lowest decoder tier that is exact for this luma offset and contrast.
+ *   3: beyond the 24-bit envelope of the fast decoder (|bright| > FAST_BRIGHT_MAX, |contrast| >= 2^23)
+ *   2: beyond the 64-bit-mad tiers -- they need the luma coefficients in [2^15, 1.5 * 2^16), the chroma ones below 2^15, no luma
+ *      stage product that wraps in the reference, |bright| <= T0_BRIGHT_MAX, and a contrast product that does not wrap either
+ *   0: everything else
+ */
+int
+crt_setup_decoder_floor(const crthip_params *p, int bright, int contrast)
+{
+    const long b = bright < 0 ? -(long) bright : (long) bright;
+    const long ct = contrast < 0 ? -(long) contrast : (long) contrast;
+    int coef_ok, cas, k;
+    long vmax;
+
+    if (b > FAST_BRIGHT_MAX || ct >= (1L << 23)) {
+        return 3;
+    }
+    /* the 64-bit-mad tiers: luma coefficients near 2^16 (the form x' = hi32(((c - 2^16) << 16) * d + {2^31, u})), chroma ones
+     * below 2^15 */
+    coef_ok = p->eq_lf[0] >= 32768 && p->eq_lf[0] < 98304 && p->eq_hf[0] >= 32768 && p->eq_hf[0] < 98304 &&
+              p->eq_lf[1] > 0 && p->eq_lf[1] < 32768 && p->eq_hf[1] > 0 && p->eq_hf[1] < 32768 &&
+              p->eq_lf[2] > 0 && p->eq_lf[2] < 32768 && p->eq_hf[2] > 0 && p->eq_hf[2] < 32768;
+    /* ... and no luma stage may wrap in the reference: stage k of a cascade with alpha = c / 2^16 obeys
+     * |x_k| <= (alpha |x_(k-1)| + 1) / (1 - |1 - alpha|), its product is c * (x_(k-1) - x_k) */
+    for (cas = 0; cas < 2 && coef_ok; cas++) {
+        const double cf = cas ? p->eq_hf[0] : p->eq_lf[0], al = cf / 65536.0, den = 1.0 - (al > 1.0 ? al - 1.0 : 1.0 - al);
+        double prev = 127.0 + (double) b, worst = 0.0;
+        for (k = 0; k < 4; k++) {
+            const double cur = (al * prev + 1.0) / den + 1.0;
+            if (prev + cur > worst) worst = prev + cur;
+            prev = cur;
+        }
+        if (cf * worst + 32768.0 >= 2147483647.0) coef_ok = 0;
+    }
+    if (!coef_ok || b > T0_BRIGHT_MAX) {
+        return 2;
+    }
+    /* ... and ((v >> 12) * contrast) >> 8 must not wrap in the reference, because tiers 0 / 1 take it from an exact 64-bit
+     * product (D9): |luma| <= 10 U + 64 with U = 127 + |bright| (both luma gain sets), |chroma| <= 3870,
+     * |v| <= 4 * 4095 * |luma| + (4530 + 7021) * |chroma| */
+    vmax = 16380L * (10L * (127 + b) + 64) + 11551L * 3870L;
+    if (((vmax >> 12) + 1) * ct >= (1L << 31)) {
+        return 2;
+    }
+    return 0;
 }
 
 /* ------------------------------------------------------------------------- */

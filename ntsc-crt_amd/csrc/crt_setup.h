@@ -50,6 +50,13 @@ int  crt_setup_bpp4fmt(int format);               /* crt_core.c:63-78 */
 /* decoder envelope helpers (see crt_setup.c) */
 void crt_setup_signal_range(const crthip_params *p, int *lo, int *hi);
 int  crt_setup_loskip_bound(int lo, int hi);
+/* The floor of the decoder tier (crt_decode_lane.h: 0 = the 64-bit-mad tiers, 2 = 24-bit multiplies, 3 = exact 32-bit ones) that a
+ * luma offset `bright` (crthip_params.bright) and a `contrast` put under every line decoded with them, for the equaliser coefficients
+ * of p -- the one definition behind the batch-wide floor of the uniform entry points (decoder_min_tier, crt_decode.hip) and the
+ * per-field floor of crthip_knobs_prepare5.  The context's switches (crthip_set_exact) are the caller's business. */
+#define T0_BRIGHT_MAX     2600            /* |bright| bound of decoder tiers 0 and 1  */
+#define FAST_BRIGHT_MAX   130000          /* |bright| bound of the fast decoder        */
+int  crt_setup_decoder_floor(const crthip_params *p, int bright, int contrast);
 
 /* VHS rand() model (see crt_setup.c) */
 void crt_setup_vhs_power(unsigned long k, unsigned c[31]);

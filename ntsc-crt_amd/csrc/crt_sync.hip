@@ -166,8 +166,10 @@ __device__ __forceinline__ int burst_step(int acc, int s)
  * `padv` valid bytes of the next line's head behind each.  Every window below is then addressed through sig_phys (line and column
  * of its first byte; contiguous from there), the line table's pos becomes an offset in the padded field, and the few lines whose
  * decoder window would run past the valid copy (hsync far from lock) get that window copied into a scratch row behind the field. */
-/* KN: monitor hue and saturation (and, k_bloom, the noise term of max_e) of the wave's field from its crthip_knob_rec (crt_dev.h) */
-template <class S, int FPB, bool PAD, bool KN = false>
+/* KN: monitor hue and saturation (and, k_bloom, the noise term of max_e) of the wave's field from its crthip_knob_rec (crt_dev.h);
+ * KN == 2 (picture knobs, crthip_knobs_prepare5): the record's tier floor -- what the field's brightness and contrast ask of the
+ * decoder -- is ORed into the tier flags of every line of the field as well */
+template <class S, int FPB, bool PAD, int KN = 0>
 __global__ void __launch_bounds__(64 * FPB, 4)
 k_hsync_wave(const crthip_params P, int n_fields, const signed char *__restrict__ inp, size_t fstride,
              crthip_state *__restrict__ state, crthip_line *__restrict__ lines, uint2 whole_field, int advance_rn,
@@ -207,9 +209,11 @@ k_hsync_wave(const crthip_params P, int n_fields, const signed char *__restrict_
     auto phys = [&](int a) { return PAD ? sig_phys<S>(a) : a; };
     crthip_state *st = state + f;
     int huesn = P.huesn, huecs = P.huecs, saturation = P.saturation;
-    if constexpr (KN) {
+    int floor_flags = 0;
+    if constexpr (KN != 0) {
         const crthip_knob_rec *kr = knob_blob_recs(P) + f;
         huesn = kr->huesn; huecs = kr->huecs; saturation = kr->saturation;
+        if constexpr (KN == 2) floor_flags = tier_floor_flags(__builtin_amdgcn_readfirstlane(kr->tier_floor));
     }
     int hsync = __builtin_amdgcn_readfirstlane(st->hsync);
     /* D2: the vertical sync search of this field, by the field's own wave (one launch and one trip through memory less
@@ -518,6 +522,7 @@ k_hsync_wave(const crthip_params P, int n_fields, const signed char *__restrict_
                     }
                     nrows |= (rank & CRTHIP_LINE_RANK_MASK) << CRTHIP_LINE_RANK_SHIFT;
                     nrows |= line_tier_flags<CCS>(lp.wave0, lp.wave1, saturation, P.loskip_wave_max, reads_tail);
+                    if constexpr (KN == 2) nrows |= floor_flags;
                     lp.nrows = nrows;
                 }
                 v4i a, b;
@@ -694,8 +699,11 @@ int crt_run_sync(crthip_ctx *c, const crthip_params *p, int n, const signed char
         const int shift = pad ? lay->shift : 0, padv = pad ? lay->padv : 0;
         const bool fpb4 = FPB4_OK && c->sync_kernel != 2 && (n >= SYNC_FPB4_MIN_FIELDS || c->sync_kernel == 3);
 #define CRTHIP_LAUNCH_SYNC(FPB, PADV) do { \
-    if (c->knob_recs) \
-    hipLaunchKernelGGL((k_hsync_wave<S, FPB, PADV, true>), dim3((n + FPB - 1) / FPB), dim3(64 * FPB), 0, c->stream, *p, n, d_inp, fstride, d_state, d_lines, \
+    if (knob_pic_call(c)) \
+    hipLaunchKernelGGL((k_hsync_wave<S, FPB, PADV, 2>), dim3((n + FPB - 1) / FPB), dim3(64 * FPB), 0, c->stream, *p, n, d_inp, fstride, d_state, d_lines, \
+                       c->whole_field, advance_rn, preset_ccf, shift, padv, pad ? const_cast<signed char *>(d_inp) : nullptr); \
+    else if (c->knob_recs) \
+    hipLaunchKernelGGL((k_hsync_wave<S, FPB, PADV, 1>), dim3((n + FPB - 1) / FPB), dim3(64 * FPB), 0, c->stream, *p, n, d_inp, fstride, d_state, d_lines, \
                        c->whole_field, advance_rn, preset_ccf, shift, padv, pad ? const_cast<signed char *>(d_inp) : nullptr); \
     else \
     hipLaunchKernelGGL((k_hsync_wave<S, FPB, PADV>), dim3((n + FPB - 1) / FPB), dim3(64 * FPB), 0, c->stream, *p, n, d_inp, fstride, d_state, d_lines, \
