@@ -1,6 +1,8 @@
 /* crt_host.hip -- context, the crthip_* C ABI (include/crt_hip.h), sequence mode.  See crt_dev.h. */
 #include "crt_dev.h"
 
+#include <type_traits>
+
 /* ------------------------------------------------------------------------- */
 /* Sequence mode: n consecutive fields of ONE television set  */
 /* ------------------------------------------------------------------------- */
@@ -16,20 +18,26 @@
  *             recurrence over fields);
  *   weave   : output image k = the single output buffer after field k: rows field k does not write come
  *             from the latest earlier field that wrote them (or the initial buffer). */
+/* (m, a) = J^e by square and multiply, J = whole_field: rn -> m * rn + a is e whole fields of the LCG */
+__device__ __forceinline__ uint2 lcg_pow(uint2 whole_field, unsigned e)
+{
+    unsigned pm = whole_field.x, pa = whole_field.y, m = 1u, a = 0u;
+    for (; e; e >>= 1) {
+        if (e & 1u) { m = pm * m; a = pm * a + pa; }
+        pa = pm * pa + pa;
+        pm = pm * pm;
+    }
+    return make_uint2(m, a);
+}
+
 /* state[k].rn = J^(first_index + k)(rn0): the set's generator before field first_index + k of the video, rn0 = before
  * field 0 (a shard of a longer video starts at first_index > 0) */
 __global__ void k_seq_rn(int n_fields, crthip_state *state, uint2 whole_field, unsigned first_index, unsigned rn0)
 {
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= n_fields) return;
-    /* (m, a) = J^e by square and multiply */
-    unsigned pm = whole_field.x, pa = whole_field.y, m = 1u, a = 0u;
-    for (unsigned e = first_index + (unsigned) k; e; e >>= 1) {
-        if (e & 1u) { m = pm * m; a = pm * a + pa; }
-        pa = pm * pa + pa;
-        pm = pm * pm;
-    }
-    state[k].rn = (int) (m * rn0 + a);
+    const uint2 j = lcg_pow(whole_field, first_index + (unsigned) k);
+    state[k].rn = (int) (j.x * rn0 + j.y);
 }
 
 /* init_k = (k ? guess[k-1] : first); also remembers nothing else */
@@ -68,16 +76,24 @@ __global__ void k_seq_rows(int n_fields, int lines_per_field, int outh, const cr
     }
 }
 
-/* latest[k][row] = last field <= k that wrote the row, -1 = none (serial in k, one lane per row) */
+/* latest[k][r] for the fields [range[0], range[1]) of one set = the last field of the set, <= k, that wrote row r (an absolute field
+ * index), -1 = none: serial in k, one lane per (set, row).  The range is read where it lies: k_seq_latest's is in registers, a set
+ * table in memory is read again every field (the compiler cannot know that `latest` does not overlap it). */
+__device__ __forceinline__ void latest_column(const int *range, int r, int outh, const unsigned char *owner, int *latest)
+{
+    int last = -1;
+    for (int k = range[0]; k < range[1]; k++) {
+        if (owner[(size_t) k * outh + r]) last = k;
+        latest[(size_t) k * outh + r] = last;
+    }
+}
+
 __global__ void k_seq_latest(int n_fields, int outh, const unsigned char *owner, int *latest)
 {
     const int r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= outh) return;
-    int last = -1;
-    for (int k = 0; k < n_fields; k++) {
-        if (owner[(size_t) k * outh + r]) last = k;
-        latest[(size_t) k * outh + r] = last;
-    }
+    const int range[2] = { 0, n_fields };
+    latest_column(range, r, outh, owner, latest);
 }
 
 /* Display modes (CRTHIP_F_PHOSPHOR_FADE / _CLEAR, crt_hip.h): what happens to the output buffer before every field.  KEEP = carried
@@ -94,23 +110,12 @@ __device__ __forceinline__ unsigned phos_fade1(unsigned c) { return (c >> 1) + (
 /* byte `o` of a row (rows start on a pixel) is the alpha byte of its pixel */
 __device__ __forceinline__ bool phos_is_alpha(size_t o, unsigned alpha_mask) { return ((alpha_mask >> (8 * (o & 3))) & 0xffu) != 0; }
 
-/* rows of image k that field k did not write <- the same row of image latest[k][row] (or the initial image).
- * FADE: that row is age = k - latest fields old (k + 1 for the initial image) and gets fade^age, which is uniform over the block:
- * a loop of `age` word fades (all zeros from CRTHIP_PHOSPHOR_DEPTH on, without reading the source).  CLEAR: zeros. */
+/* one row of the weave, by a block of 256: dst <- src (nullptr: zeros) as it looks `age` fields later.  FADE: fade^age, which is
+ * uniform over the block: a loop of `age` word fades (all zeros from CRTHIP_PHOSPHOR_DEPTH on, without reading the source).
+ * CLEAR: zeros, without reading the source.  16-byte strips, the last bytes of a row one by one. */
 template <int PH>
-__global__ void __launch_bounds__(256)
-k_seq_weave(int n_fields, int outh, size_t pitch, unsigned char *out, size_t ostride, const unsigned char *init,
-            const int *latest, int patch_only, unsigned alpha_mask)
+__device__ __forceinline__ void weave_row(unsigned char *dst, const unsigned char *src, int age, size_t pitch, unsigned alpha_mask)
 {
-    const int row = blockIdx.x % outh, k = blockIdx.x / outh;
-    if (k >= n_fields) return;
-    const int src_k = latest[(size_t) k * outh + row];
-    if (src_k == k) return;
-    if (patch_only && src_k >= 0) return;       /* second visit (cross-shard chain): only the rows nobody here wrote */
-    unsigned char *dst = out + (size_t) k * ostride + (size_t) row * pitch;
-    const unsigned char *src = src_k >= 0 ? out + (size_t) src_k * ostride + (size_t) row * pitch
-                                          : (init ? init + (size_t) row * pitch : nullptr);
-    const int age = PH == PH_FADE ? (src_k >= 0 ? k - src_k : k + 1) : 0;
     if (PH == PH_CLEAR || age >= CRTHIP_PHOSPHOR_DEPTH) src = nullptr;
     for (size_t b = (size_t) threadIdx.x * 16; b < pitch; b += 256 * 16) {
         const size_t nb = pitch - b < 16 ? pitch - b : 16;
@@ -134,6 +139,25 @@ k_seq_weave(int n_fields, int outh, size_t pitch, unsigned char *out, size_t ost
             }
         }
     }
+}
+
+/* rows of image k that field k did not write <- the same row of image latest[k][row], k - latest fields old (or the initial image,
+ * k + 1 fields old) */
+template <int PH>
+__global__ void __launch_bounds__(256)
+k_seq_weave(int n_fields, int outh, size_t pitch, unsigned char *out, size_t ostride, const unsigned char *init,
+            const int *latest, int patch_only, unsigned alpha_mask)
+{
+    const int row = blockIdx.x % outh, k = blockIdx.x / outh;
+    if (k >= n_fields) return;
+    const int src_k = latest[(size_t) k * outh + row];
+    if (src_k == k) return;
+    if (patch_only && src_k >= 0) return;       /* second visit (cross-shard chain): only the rows nobody here wrote */
+    unsigned char *dst = out + (size_t) k * ostride + (size_t) row * pitch;
+    const unsigned char *src = src_k >= 0 ? out + (size_t) src_k * ostride + (size_t) row * pitch
+                                          : (init ? init + (size_t) row * pitch : nullptr);
+    const int age = PH == PH_FADE ? (src_k >= 0 ? k - src_k : k + 1) : 0;
+    weave_row<PH>(dst, src, age, pitch, alpha_mask);
 }
 
 /* (field-pass) one display step of FADE / CLEAR on every image of the batch, each its own display, before the decoder writes
@@ -205,8 +229,42 @@ __global__ void k_seq_rowsrc(int n_fields, int lines_per_field, int outh, const 
     }
 }
 
-/* FADE: the old word is faded in registers first (the picture the decoder blends against is the faded one, and rows field k
- * does not write become fade(prev)); CLEAR: the old picture is all zeros and is not read */
+/* one word of that recurrence: `o` = the old word, already taken at the row the line started on (the word is one pixel of a 4-byte
+ * format, or four bytes of a 3-byte one with alpha_mask 0).  FADE: the old word is faded in registers first (the picture the
+ * decoder blends against is the faded one, and rows field k does not write become fade(prev)), then its alpha is cleared; CLEAR:
+ * the old picture is all zeros.  A written word: every colour byte (new >> 1) + (old >> 1) -- what the 0xfefeff mask computes per
+ * channel -- and alpha stays 0xff; an unwritten one passes `o` through. */
+template <int PH> __device__ __forceinline__ unsigned fold_word(unsigned n, unsigned o, bool written, unsigned alpha_mask)
+{
+    if (PH == PH_CLEAR) o = 0u;
+    if (PH == PH_FADE) o = phos_fade4(o) & ~alpha_mask;
+    return written ? ((((n >> 1) & 0x7f7f7f7fu) + ((o >> 1) & 0x7f7f7f7fu)) | alpha_mask) : o;
+}
+
+/* one row of one field's step, by a block of 256: cur = image k's row, src = its rowsrc entry, prev_img = image k - 1 or the initial
+ * picture (nullptr: zeros, as calloc leaves them -- also what CLEAR makes of it without reading it, so fold_word's `o = 0` and the
+ * unread pointer are the same rule).  Written out by hand for one field of one set -- o = fade4(o) & ~alpha under FADE, then
+ * v = src < 0 ? o : ((n >> 1) & 0x7f7f7f7f) + ((o >> 1) & 0x7f7f7f7f) | alpha -- the step is fold_word with written = (src >= 0),
+ * so k_seq_blend_step and k_sets_blend_step share this body.  I = the type of the byte counter of a word, the one thing the compiler
+ * does not see through: size_t (k_seq_blend_step) costs 20 registers, int (k_sets_blend_step) 18, and neither has been measured
+ * against the other, so each kernel names its own. */
+template <int PH, class I>
+__device__ __forceinline__ void blend_row(unsigned char *cur, const unsigned char *prev_img, int row, int src, size_t pitch, unsigned alpha_mask)
+{
+    if (PH == PH_CLEAR) prev_img = nullptr;
+    const unsigned char *old = prev_img ? prev_img + (size_t) (src < 0 ? row : src) * pitch : nullptr;
+    for (size_t b = (size_t) threadIdx.x * 4; b < pitch; b += 256 * 4) {
+        const I nb = pitch - b < 4 ? (I) (pitch - b) : 4;
+        unsigned o = 0, n = 0;
+        for (I c = 0; c < nb; c++) {
+            o |= (unsigned) (old ? old[b + c] : 0) << (8 * c);
+            n |= (unsigned) cur[b + c] << (8 * c);
+        }
+        const unsigned v = fold_word<PH>(n, o, src >= 0, alpha_mask);
+        for (I c = 0; c < nb; c++) cur[b + c] = (unsigned char) (v >> (8 * c));
+    }
+}
+
 template <int PH>
 __global__ void __launch_bounds__(256)
 k_seq_blend_step(int k, int outh, size_t pitch, unsigned char *out, size_t ostride, const unsigned char *init,
@@ -215,20 +273,7 @@ k_seq_blend_step(int k, int outh, size_t pitch, unsigned char *out, size_t ostri
     const int row = blockIdx.x;
     const int src = rowsrc[(size_t) k * outh + row];
     unsigned char *cur = out + (size_t) k * ostride + (size_t) row * pitch;
-    const unsigned char *prev_img = PH == PH_CLEAR ? nullptr : (k ? out + (size_t) (k - 1) * ostride : init);   /* nullptr: zeros (calloc) */
-    const unsigned char *old = prev_img ? prev_img + (size_t) (src < 0 ? row : src) * pitch : nullptr;
-    for (size_t b = (size_t) threadIdx.x * 4; b < pitch; b += 256 * 4) {
-        const size_t nb = pitch - b < 4 ? pitch - b : 4;
-        unsigned o = 0, n = 0;
-        for (size_t c = 0; c < nb; c++) {
-            o |= (unsigned) (old ? old[b + c] : 0) << (8 * c);
-            n |= (unsigned) cur[b + c] << (8 * c);
-        }
-        if (PH == PH_FADE) o = phos_fade4(o) & ~alpha_mask;      /* b is a multiple of 4: the word is one pixel of a 4-byte format */
-        /* every colour byte: (new >> 1) + (old >> 1) -- what the 0xfefeff mask computes per channel; alpha stays 0xff */
-        const unsigned v = src < 0 ? o : ((((n >> 1) & 0x7f7f7f7fu) + ((o >> 1) & 0x7f7f7f7fu)) | alpha_mask);
-        for (size_t c = 0; c < nb; c++) cur[b + c] = (unsigned char) (v >> (8 * c));
-    }
+    blend_row<PH, size_t>(cur, k ? out + (size_t) (k - 1) * ostride : init, row, src, pitch, alpha_mask);
 }
 
 /* ------------------------------------------------------------------------- */
@@ -254,13 +299,8 @@ __global__ void k_sets_rn(int n_fields, crthip_state *state, const int2 *tab, co
     if (k >= n_fields) return;
     const int2 t = tab[k];
     const int4 in = inc[t.y];
-    unsigned pm = whole_field.x, pa = whole_field.y, m = 1u, a = 0u;
-    for (unsigned e = (unsigned) (k - t.x); e; e >>= 1) {
-        if (e & 1u) { m = pm * m; a = pm * a + pa; }
-        pa = pm * pa + pa;
-        pm = pm * pm;
-    }
-    state[k].rn = (int) (m * (unsigned) in.z + a);
+    const uint2 j = lcg_pow(whole_field, (unsigned) (k - t.x));
+    state[k].rn = (int) (j.x * (unsigned) in.z + j.y);
     guess[k] = make_int2(in.x, in.y);
 }
 
@@ -286,17 +326,13 @@ __global__ void k_sets_load(int n_fields, crthip_state *state, const int2 *tab, 
     state[k].vsync = v.y;
 }
 
-/* latest[k][row] = last field of k's set, <= k, that wrote the row (an absolute field index), -1 = none: one lane per (set, row) */
+/* k_seq_latest per set: one lane per (set, row) */
 __global__ void k_sets_latest(int n_sets, int outh, const int *set_first, const unsigned char *owner, int *latest)
 {
     const int gid = blockIdx.x * blockDim.x + threadIdx.x;
     if (gid >= n_sets * outh) return;
-    const int s = gid / outh, r = gid - s * outh;
-    int last = -1;
-    for (int k = set_first[s]; k < set_first[s + 1]; k++) {
-        if (owner[(size_t) k * outh + r]) last = k;
-        latest[(size_t) k * outh + r] = last;
-    }
+    const int s = gid / outh;
+    latest_column(set_first + s, gid - s * outh, outh, owner, latest);
 }
 
 /* k_seq_weave with the set boundary: the initial picture is the one of the field's own set, and it is k - first + 1 fields old */
@@ -314,29 +350,7 @@ k_sets_weave(int n_fields, int outh, size_t pitch, unsigned char *out, size_t os
     const unsigned char *src = src_k >= 0 ? out + (size_t) src_k * ostride + (size_t) row * pitch
                                           : (init ? init + (size_t) t.y * init_stride + (size_t) row * pitch : nullptr);
     const int age = PH == PH_FADE ? (src_k >= 0 ? k - src_k : k - t.x + 1) : 0;
-    if (PH == PH_CLEAR || age >= CRTHIP_PHOSPHOR_DEPTH) src = nullptr;
-    for (size_t b = (size_t) threadIdx.x * 16; b < pitch; b += 256 * 16) {
-        const size_t nb = pitch - b < 16 ? pitch - b : 16;
-        if (nb == 16) {
-            v4i v = { 0, 0, 0, 0 };
-            if (src) v = load16u(src + b);
-            if (PH == PH_FADE && src) {
-                unsigned w0 = (unsigned) v.x, w1 = (unsigned) v.y, w2 = (unsigned) v.z, w3 = (unsigned) v.w;
-                for (int a = 0; a < age; a++) { w0 = phos_fade4(w0); w1 = phos_fade4(w1); w2 = phos_fade4(w2); w3 = phos_fade4(w3); }
-                v.x = (int) (w0 & ~alpha_mask); v.y = (int) (w1 & ~alpha_mask); v.z = (int) (w2 & ~alpha_mask); v.w = (int) (w3 & ~alpha_mask);
-            }
-            store16u(dst + b, v);
-        } else {
-            for (size_t c = 0; c < nb; c++) {
-                unsigned x = src ? src[b + c] : 0u;
-                if (PH == PH_FADE && src) {
-                    for (int a = 0; a < age; a++) x = phos_fade1(x);
-                    if (phos_is_alpha(b + c, alpha_mask)) x = 0;
-                }
-                dst[b + c] = (unsigned char) x;
-            }
-        }
-    }
+    weave_row<PH>(dst, src, age, pitch, alpha_mask);
 }
 
 /* 16 bytes of a row, or the nb < 16 that are left of it (zero filled) */
@@ -354,14 +368,6 @@ __device__ __forceinline__ void strip_store(unsigned char *p, v4i v, int nb)
     const unsigned w[4] = { (unsigned) v.x, (unsigned) v.y, (unsigned) v.z, (unsigned) v.w };
     for (int c = 0; c < nb; c++) p[c] = (unsigned char) (w[c >> 2] >> (8 * (c & 3)));
 }
-/* one word of the recurrence of k_seq_blend_step: `o` = the old word (already taken at the row the line started on) */
-template <int PH> __device__ __forceinline__ unsigned fold_word(unsigned n, unsigned o, bool written, unsigned alpha_mask)
-{
-    if (PH == PH_CLEAR) o = 0u;
-    if (PH == PH_FADE) o = phos_fade4(o) & ~alpha_mask;
-    return written ? ((((n >> 1) & 0x7f7f7f7fu) + ((o >> 1) & 0x7f7f7f7fu)) | alpha_mask) : o;
-}
-
 /* blend != 0 for all sets in ONE launch.  The recurrence v_k[row] = src < 0 ? f(v_{k-1}[row]) : blend(new_k[row], f(v_{k-1}[src]))
  * takes the old value at row src = the first row of the line that wrote `row`, so with duplicated rows a row's chain crosses into
  * other rows from field to field: rows are not independent -- but byte columns are.  A workgroup owns one set x one strip of 16
@@ -426,20 +432,9 @@ k_sets_blend_step(int j, int outh, size_t pitch, unsigned char *out, size_t ostr
     if (k >= set_first[s + 1]) return;
     const int src = rowsrc[(size_t) k * outh + row];
     unsigned char *cur = out + (size_t) k * ostride + (size_t) row * pitch;
-    const unsigned char *prev_img = PH == PH_CLEAR ? nullptr : (j ? out + (size_t) (k - 1) * ostride : (init ? init + (size_t) s * init_stride : nullptr));
-    const unsigned char *old = prev_img ? prev_img + (size_t) (src < 0 ? row : src) * pitch : nullptr;
-    for (size_t b = (size_t) threadIdx.x * 4; b < pitch; b += 256 * 4) {
-        const int nb = pitch - b < 4 ? (int) (pitch - b) : 4;
-        unsigned o = 0, n = 0;
-        for (int c = 0; c < nb; c++) {
-            o |= (unsigned) (old ? old[b + c] : 0) << (8 * c);
-            n |= (unsigned) cur[b + c] << (8 * c);
-        }
-        const unsigned v = fold_word<PH>(n, o, src >= 0, alpha_mask);
-        for (int c = 0; c < nb; c++) cur[b + c] = (unsigned char) (v >> (8 * c));
-    }
+    const unsigned char *prev_img = j ? out + (size_t) (k - 1) * ostride : (init ? init + (size_t) s * init_stride : nullptr);
+    blend_row<PH, int>(cur, prev_img, row, src, pitch, alpha_mask);
 }
-
 
 /* ------------------------------------------------------------------------- */
 /* Stills (crthip_stills): several field-passes of the same images onto the same pictures */
@@ -528,6 +523,15 @@ bool crt_fused_layout(const crthip_ctx *c, const crthip_params *p, int n, sig_la
     return layout_rule(c->system, c->pattern, c->sd, c->fstride, p, n, c->shape, c->sig_pad, lay);
 }
 
+/* the reference's flat layout: what a field-pass falls back to, and what sequence mode always keeps (its phases are separate calls
+ * over the same workspace) */
+static sig_layout flat_layout(const crthip_ctx *c)
+{
+    sig_layout lay;
+    lay.pitch = c->sd.hres; lay.shift = 0; lay.padv = 0; lay.wrap = 0; lay.fstride = c->fstride;
+    return lay;
+}
+
 /* the byte the decoder writes 0xff into (crt_core.c:620-652): byte 3 of RGBA / BGRA, byte 0 of ARGB / ABGR, none for RGB / BGR */
 static unsigned out_alpha_mask(const crthip_params *p)
 {
@@ -540,22 +544,36 @@ static int phosphor_mode(const crthip_params *p)
     return (p->flags & CRTHIP_F_PHOSPHOR_FADE) ? PH_FADE : (p->flags & CRTHIP_F_PHOSPHOR_CLEAR) ? PH_CLEAR : PH_KEEP;
 }
 
-/* a field-pass's display step on fields [0, n) of `out` (their line tables at `ln`), before their decoder runs */
-template <int PH>
-static void launch_phosphor_rows(crthip_ctx *c, const crthip_params *p, int n, const crthip_line *ln, unsigned char *out, size_t ostride)
+/* f(std::integral_constant<int, PH_*>{}) for the display mode `ph`, in the idiom of dispatch_system: the one place that turns the
+ * run-time mode into the kernels' template argument */
+template <class F> static void dispatch_phosphor(int ph, F &&f)
 {
-    const int rb = (p->outh + PHOS_ROWS - 1) / PHOS_ROWS;
-    const size_t pitch = (size_t) p->outw * p->out_bpp;
-    const dim3 grid((unsigned) n * (unsigned) rb);
-    if (p->blend)
-        hipLaunchKernelGGL((k_phosphor_rows<PH, true>), grid, dim3(256), 0, c->stream, n, c->sd.lines, p->outh, rb, pitch, out, ostride, ln,
-                           out_alpha_mask(p));
-    else
-        hipLaunchKernelGGL((k_phosphor_rows<PH, false>), grid, dim3(256), 0, c->stream, n, c->sd.lines, p->outh, rb, pitch, out, ostride, ln,
-                           out_alpha_mask(p));
+    if (ph == PH_FADE) f(std::integral_constant<int, PH_FADE>{});
+    else if (ph == PH_CLEAR) f(std::integral_constant<int, PH_CLEAR>{});
+    else f(std::integral_constant<int, PH_KEEP>{});
 }
 
-/* crthip_sequence_sets: its scratch (sets_scratch below) and the last phase, by display mode */
+/* a field-pass's display step on fields [0, n) of `out` (their line tables at `ln`), before their decoder runs: CRTHIP_F_PHOSPHOR_*,
+ * displaycb's fade / clear (crt_main.c:459-463) between the sync chain and the decoder; KEEP has none */
+static void launch_phosphor_rows(crthip_ctx *c, const crthip_params *p, int n, const crthip_line *ln, unsigned char *out, size_t ostride)
+{
+    dispatch_phosphor(phosphor_mode(p), [&](auto ph) {
+        constexpr int PH = decltype(ph)::value;
+        if constexpr (PH != PH_KEEP) {
+            const int rb = (p->outh + PHOS_ROWS - 1) / PHOS_ROWS;
+            const size_t pitch = (size_t) p->outw * p->out_bpp;
+            const dim3 grid((unsigned) n * (unsigned) rb);
+            if (p->blend)
+                hipLaunchKernelGGL((k_phosphor_rows<PH, true>), grid, dim3(256), 0, c->stream, n, c->sd.lines, p->outh, rb, pitch, out, ostride, ln,
+                                   out_alpha_mask(p));
+            else
+                hipLaunchKernelGGL((k_phosphor_rows<PH, false>), grid, dim3(256), 0, c->stream, n, c->sd.lines, p->outh, rb, pitch, out, ostride, ln,
+                                   out_alpha_mask(p));
+        }
+    });
+}
+
+/* scratch of sequence mode (seq_carve below), and the last phase of crthip_sequence_sets by display mode */
 struct SetsScratch { int *set_first; int2 *tab; int4 *inc; int2 *guess; int *changed; unsigned char *owner; int *latest; };
 template <int PH>
 static void launch_sets_weave(crthip_ctx *c, const crthip_params *p, int n_sets, int n, int max_len, unsigned char *out, size_t ostride,
@@ -1012,9 +1030,7 @@ static int fieldpass_chunk(crthip_ctx *c, const crthip_params *p, int enc, int f
         if (rc) return rc;
     }
     if ((part & 2) && p->out_bpp != 0) {
-        /* CRTHIP_F_PHOSPHOR_*: displaycb's fade / clear (crt_main.c:459-463) between the sync chain and the decoder */
-        if (phosphor_mode(p) == PH_FADE) launch_phosphor_rows<PH_FADE>(c, p, n, ln, out, ostride);
-        else if (phosphor_mode(p) == PH_CLEAR) launch_phosphor_rows<PH_CLEAR>(c, p, n, ln, out, ostride);
+        launch_phosphor_rows(c, p, n, ln, out, ostride);
         rc = crt_run_decode(c, p, n, inp, ln, out, ostride, lay.fstride);
     }
     return rc;
@@ -1049,9 +1065,7 @@ static int fieldpass_body(crthip_ctx *c, const crthip_params *p, int n, const vo
     /* the signal between this call's encoder and decoder: padded lines where the fused LCG-noise encoder writes it (crt_dev.h) */
     sig_layout lay;
     const bool vhs_rand_path = c->system == CRTHIP_SYSTEM_NTSCVHS && !(p->flags & CRTHIP_F_VHS_LCG_NOISE);
-    if (enc != 0 || vhs_rand_path || !crt_fused_layout(c, p, n, &lay)) {
-        lay.pitch = c->sd.hres; lay.shift = 0; lay.padv = 0; lay.wrap = 0; lay.fstride = c->fstride;
-    }
+    if (enc != 0 || vhs_rand_path || !crt_fused_layout(c, p, n, &lay)) lay = flat_layout(c);
     /* what crthip_fieldpass_signal may unpad is the signal of the last pass that was enqueued COMPLETELY: a pass refused half-way
      * (the decoder's argument checks come after the encoder and the sync chain) leaves no claim on the workspace */
     c->last_n = 0;
@@ -1231,9 +1245,7 @@ int crthip_stills(crthip_ctx *c, const crthip_params *p, int n, const void *d_im
     }
     /* the layout a field-pass of these n fields takes (crthip_fieldpass) */
     sig_layout lay;
-    if (enc != 0 || vhs_rand || !crt_fused_layout(c, p, n, &lay)) {
-        lay.pitch = c->sd.hres; lay.shift = 0; lay.padv = 0; lay.wrap = 0; lay.fstride = c->fstride;
-    }
+    if (enc != 0 || vhs_rand || !crt_fused_layout(c, p, n, &lay)) lay = flat_layout(c);
     c->last_n = 0;                                        /* crthip_fieldpass_signal: refused after a stills call (crt_hip.h) */
     const dim3 gn((n + 63) / 64), b64(64);
     const bool shared = p->noise == 0 && enc == 0 && !vhs_rand && !(p->flags & CRTHIP_F_NO_VSYNC) && p->out_bpp != 0;
@@ -1284,8 +1296,7 @@ int crthip_stills(crthip_ctx *c, const crthip_params *p, int n, const void *d_im
         }
         rc = crt_run_sync(c, &q, n, sig, d_state, c->d_lines, 1, preset ? 1 : 0, &lay);
         if (rc) return rc;
-        if (phosphor_mode(p) == PH_FADE) launch_phosphor_rows<PH_FADE>(c, p, n, c->d_lines, out, ostride);
-        else if (phosphor_mode(p) == PH_CLEAR) launch_phosphor_rows<PH_CLEAR>(c, p, n, c->d_lines, out, ostride);
+        launch_phosphor_rows(c, p, n, c->d_lines, out, ostride);
         rc = crt_run_decode(c, p, n, sig, c->d_lines, out, ostride, lay.fstride);
         if (rc) return rc;
     }
@@ -1351,21 +1362,36 @@ int crthip_set_pixel_tile(crthip_ctx *c, int px)
     return CRTHIP_OK;
 }
 
-/* scratch of the sequence phases: guess[n] (int2), changed flag, owner[n][outh] (u8), latest[n][outh] (int) */
-struct SeqScratch { int2 *guess; int *changed; unsigned char *owner; int *latest; };
-static int seq_scratch(crthip_ctx *c, int n, int outh, SeqScratch *sc)
+/* The scratch of sequence mode, carved from the lazily grown block c->d_seq: set_first[n_sets + 1], tab[n] (first field of my set, my
+ * set), inc[n_sets] (incoming hsync, vsync, rn) -- crthip_sequence_sets only; the phase entry points carve with n_sets == 0, which
+ * leaves the three empty --, then guess[n] (int2), the changed flag, owner[n][outh] (u8), latest[n][outh] (int).  Who may trust
+ * guess[] (c->seq_guess_n = the number of fields it holds finals for):
+ *   - a reallocation synchronises the stream first (work in flight may still use the old block) and clears seq_guess_n;
+ *   - a sets call clears seq_guess_n: its guess[] lies elsewhere in the block and holds other fields' pairs;
+ *   - phase calls with the same n carve the same offsets (none depends on outh before owner), so a second crthip_seq_sync, or one
+ *     behind crthip_seq_weave, finds guess[] where the previous one left it: the warm start across shards. */
+static int seq_carve(crthip_ctx *c, int n_sets, int n, int outh, SetsScratch *sc)
 {
-    const size_t need = sizeof(int2) * (size_t) n + 256 + (size_t) n * outh + 256 + sizeof(int) * (size_t) n * outh + 256;
+    const auto up = [](size_t v) { return (v + 255) & ~(size_t) 255; };
+    const size_t o_tab = up(sizeof(int) * ((size_t) n_sets + 1)), o_inc = o_tab + up(sizeof(int2) * (size_t) (n_sets ? n : 0));
+    const size_t o_guess = o_inc + up(sizeof(int4) * (size_t) n_sets), o_changed = o_guess + up(sizeof(int2) * (size_t) n);
+    const size_t o_owner = o_changed + 256, o_latest = o_owner + up((size_t) n * outh);
+    const size_t need = o_latest + up(sizeof(int) * (size_t) n * outh);
     if (need > c->seq_cap) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
         if (c->d_seq) hipFree(c->d_seq);
         c->d_seq = 0; c->seq_cap = 0; c->seq_guess_n = 0;
         if (hipMalloc((void **) &c->d_seq, need) != hipSuccess) return set_err(c, CRTHIP_E_NOMEM, "hipMalloc sequence scratch", hipSuccess);
         c->seq_cap = need;
     }
-    sc->guess = (int2 *) c->d_seq;
-    sc->changed = (int *) (c->d_seq + sizeof(int2) * (size_t) n);
-    sc->owner = c->d_seq + sizeof(int2) * (size_t) n + 256;
-    sc->latest = (int *) (sc->owner + (((size_t) n * outh + 255) & ~(size_t) 255));
+    if (n_sets) c->seq_guess_n = 0;
+    sc->set_first = (int *) c->d_seq;
+    sc->tab = (int2 *) (c->d_seq + o_tab);
+    sc->inc = (int4 *) (c->d_seq + o_inc);
+    sc->guess = (int2 *) (c->d_seq + o_guess);
+    sc->changed = (int *) (c->d_seq + o_changed);
+    sc->owner = c->d_seq + o_owner;
+    sc->latest = (int *) (c->d_seq + o_latest);
     return CRTHIP_OK;
 }
 
@@ -1382,6 +1408,75 @@ static int seq_check(crthip_ctx *c, const crthip_params *p, int n)
     if (p->out_bpp == 0) return set_err(c, CRTHIP_E_ARG, "sequence mode: unknown output pixel format", hipSuccess);
     int enc = check_encoder(c, p);
     if (enc != 0) return enc < 0 ? enc : set_err(c, CRTHIP_E_ARG, "sequence mode: unknown input pixel format", hipSuccess);
+    return CRTHIP_OK;
+}
+
+/* What the single-set phases and crthip_sequence_sets have in common, each piece once. */
+
+/* every field's noisy signal into c->d_inp, the states' generators already set.  vhs (the stock VHS build, whose noise follows
+ * rand()): clean encode into c->d_analog, then the rand() noise (which also leaves rn), as in crthip_fieldpass; otherwise one fused
+ * encode (noise fused, ccf presets) */
+static int seq_signal(crthip_ctx *c, const crthip_params *p, int n, const void *d_images, size_t istride, crthip_state *d_state, bool vhs)
+{
+    if (!vhs) return crt_run_encoder(c, p, n, d_images, istride, c->d_inp, d_state, true, 1, false);
+    crthip_params clean = *p;
+    clean.noise = 0;
+    const int rc = crt_run_encoder(c, &clean, n, d_images, istride, c->d_analog, d_state, true, 1, false);
+    if (rc) return rc;
+    return crt_run_noise(c, p, n, c->d_analog, c->d_inp, d_state, false);
+}
+
+/* sequence mode keeps the reference's flat signal layout: recorded once the signal of all n fields is enqueued */
+static void seq_record_layout(crthip_ctx *c, int n) { c->last_lay = flat_layout(c); c->last_n = n; }
+
+/* The sync fixed point over n fields whose signal is in c->d_inp (see the comment at the top).  Per pass: `load` enqueues the
+ * caller's kernel that gives every field its initial pair -- the previous field's pair of sc.guess, or the incoming pair of its
+ * set --, then the ccf preset (crt_ntsc.c:325-329), the sync chain, and k_seq_compare (guess <- finals, one flag for all fields).
+ * After pass j the first j fields of every set are final, so more than `limit` = longest set + 1 passes cannot happen; `stuck` is
+ * what the caller says if it does (say so instead of returning a half-converged chain).  The blob the chain runs on: the
+ * envelope of a signal produced here (with_signal_envelope), or with records the envelope at their widest noise
+ * (crthip_knobs_prepare). */
+extern "C++" template <class Load>
+int seq_converge(crthip_ctx *c, const crthip_params *p, int n, crthip_state *d_state, const SetsScratch &sc, int limit,
+                 const char *stuck, int *passes_out, Load &&load)
+{
+    crthip_params q = c->knob_recs ? *p : with_signal_envelope(p);
+    if (c->knob_recs) q.loskip_wave_max = c->knob_loskip;
+    const dim3 gn((n + 63) / 64), b64(64);
+    for (int passes = 1;; passes++) {
+        HIPCHK(c, hipMemsetAsync(sc.changed, 0, sizeof(int), c->stream));
+        load();
+        int rc = crt_run_encoder_state(c, p, n, d_state);
+        if (rc) return rc;
+        rc = crt_run_sync(c, &q, n, c->d_inp, d_state, c->d_lines, 0);
+        if (rc) return rc;
+        hipLaunchKernelGGL(k_seq_compare, gn, b64, 0, c->stream, n, d_state, sc.guess, sc.changed);
+        int flag = 0;
+        HIPCHK(c, hipMemcpyAsync(&flag, sc.changed, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (!flag) {
+            if (passes_out) *passes_out = passes;
+            return CRTHIP_OK;
+        }
+        if (passes > limit) return set_err(c, CRTHIP_E_HIP, stuck, hipSuccess);
+    }
+}
+
+/* the row tables of the last phase from c->d_lines, for the sets of sc.set_first or (n_sets == 0) the single range [0, n).  With
+ * blend: sc.latest = rowsrc (k_seq_rowsrc, -1 where nobody wrote); without: sc.owner, then sc.latest = the latest writer per set */
+static int seq_row_tables(crthip_ctx *c, const crthip_params *p, int n_sets, int n, const SetsScratch &sc)
+{
+    const int outh = p->outh;
+    const dim3 gl((n * c->sd.lines + 255) / 256), b256(256);
+    if (p->blend) {
+        HIPCHK(c, hipMemsetAsync(sc.latest, 0xff, sizeof(int) * (size_t) n * outh, c->stream));       /* -1 everywhere */
+        hipLaunchKernelGGL(k_seq_rowsrc, gl, b256, 0, c->stream, n, c->sd.lines, outh, c->d_lines, sc.latest);
+        return CRTHIP_OK;
+    }
+    HIPCHK(c, hipMemsetAsync(sc.owner, 0, (size_t) n * outh, c->stream));
+    hipLaunchKernelGGL(k_seq_rows, gl, b256, 0, c->stream, n, c->sd.lines, outh, c->d_lines, sc.owner);
+    if (n_sets) hipLaunchKernelGGL(k_sets_latest, dim3((n_sets * outh + 63) / 64), dim3(64), 0, c->stream, n_sets, outh, sc.set_first, sc.owner, sc.latest);
+    else hipLaunchKernelGGL(k_seq_latest, dim3((outh + 63) / 64), dim3(64), 0, c->stream, n, outh, sc.owner, sc.latest);
     return CRTHIP_OK;
 }
 
@@ -1409,31 +1504,19 @@ static int seq_encode_body(crthip_ctx *c, const crthip_params *p, int n, int fir
     c->last_n = 0;                                         /* (recorded below, once the signal is enqueued) */
     rc = crt_run_encoder_prepare(c, p, true);
     if (rc) return rc;
-    if (vhs) {
-        /* the fields share one rand() stream: run the chain ahead (k_vhs_chain: hist[k] = generator at the start
-         * of field k, aberration heights drawn in-stream if asked), after which every field is independent;
-         * then clean encode -> rand() noise (which also leaves rn), as in crthip_fieldpass */
-        if (!c->vhs_prechained) {
-            rc = crt_run_vhs_chain(c, n, d_state, (p->flags & CRTHIP_F_VHS_DRAW_ABERRATION) != 0);
-            if (rc) return rc;
-        }
-        crthip_params clean = *p;
-        clean.noise = 0;
-        rc = crt_run_encoder(c, &clean, n, d_images, istride, c->d_analog, d_state, true, 1, false);
-        if (rc) return rc;
-        rc = crt_run_noise(c, p, n, c->d_analog, c->d_inp, d_state, false);
-        if (rc) return rc;
-    } else {
+    if (!vhs) {
         hipLaunchKernelGGL(k_seq_rn, dim3((n + 63) / 64), dim3(64), 0, c->stream, n, d_state, c->whole_field,
                            (unsigned) first_index, (unsigned) rn0);
-        /* encode every field (noise fused), ccf presets */
-        rc = crt_run_encoder(c, p, n, d_images, istride, c->d_inp, d_state, true, 1, false);
+    } else if (!c->vhs_prechained) {
+        /* the fields share one rand() stream: run the chain ahead (k_vhs_chain: hist[k] = generator at the start
+         * of field k, aberration heights drawn in-stream if asked), after which every field is independent */
+        rc = crt_run_vhs_chain(c, n, d_state, (p->flags & CRTHIP_F_VHS_DRAW_ABERRATION) != 0);
         if (rc) return rc;
     }
+    rc = seq_signal(c, p, n, d_images, istride, d_state, vhs);
+    if (rc) return rc;
     HIPCHK(c, hipGetLastError());
-    /* sequence mode keeps the reference's flat signal layout (its phases are separate calls over the same workspace) */
-    c->last_lay.pitch = c->sd.hres; c->last_lay.shift = 0; c->last_lay.padv = 0; c->last_lay.wrap = 0; c->last_lay.fstride = c->fstride;
-    c->last_n = n;
+    seq_record_layout(c, n);
     return CRTHIP_OK;
 }
 
@@ -1450,10 +1533,9 @@ static int seq_sync_body(crthip_ctx *c, const crthip_params *p, int n, crthip_st
     if (!d_state || n > c->cap_fields) return CRTHIP_E_ARG;
     if ((rc = CHECK_WORD(c, d_state))) return rc;
     HIPCHK(c, hipSetDevice(c->device));
-    SeqScratch sc;
-    rc = seq_scratch(c, n, p->outh, &sc);
+    SetsScratch sc;
+    rc = seq_carve(c, 0, n, p->outh, &sc);
     if (rc) return rc;
-    const dim3 gn((n + 63) / 64), b64(64);
     if (c->seq_guess_n != n) {
         /* first guess: nobody's sync state moves */
         int2 *h = (int2 *) malloc(sizeof(int2) * (size_t) n);
@@ -1465,26 +1547,11 @@ static int seq_sync_body(crthip_ctx *c, const crthip_params *p, int n, crthip_st
         HIPCHK(c, e);
         c->seq_guess_n = n;
     }
-    int passes = 0;
-    crthip_params q = c->knob_recs ? *p : with_signal_envelope(p);    /* inp[] comes from crthip_seq_encode */
-    if (c->knob_recs) q.loskip_wave_max = c->knob_loskip;             /* the envelope at the widest noise of the records (crthip_knobs_prepare) */
-    for (;;) {
-        passes++;
-        HIPCHK(c, hipMemsetAsync(sc.changed, 0, sizeof(int), c->stream));
-        hipLaunchKernelGGL(k_seq_load, gn, b64, 0, c->stream, n, d_state, sc.guess, make_int2(hsync_in, vsync_in));
-        rc = crt_run_encoder_state(c, p, n, d_state);                 /* ccf preset, crt_ntsc.c:325-329 */
-        if (rc) return rc;
-        rc = crt_run_sync(c, &q, n, c->d_inp, d_state, c->d_lines, 0);
-        if (rc) return rc;
-        hipLaunchKernelGGL(k_seq_compare, gn, b64, 0, c->stream, n, d_state, sc.guess, sc.changed);
-        int flag = 0;
-        HIPCHK(c, hipMemcpyAsync(&flag, sc.changed, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (!flag) break;
-        if (passes > n + 1)               /* after pass k fields 0 .. k-1 are final: cannot happen (say so instead of returning a half-converged chain) */
-            return set_err(c, CRTHIP_E_HIP, "crthip_seq_sync: the sync chain over the fields did not converge", hipSuccess);
-    }
-    if (passes_out) *passes_out = passes;
+    rc = seq_converge(c, p, n, d_state, sc, n + 1, "crthip_seq_sync: the sync chain over the fields did not converge", passes_out,
+                      [&] {
+        hipLaunchKernelGGL(k_seq_load, dim3((n + 63) / 64), dim3(64), 0, c->stream, n, d_state, sc.guess, make_int2(hsync_in, vsync_in));
+    });
+    if (rc) return rc;
     if (hsync_out || vsync_out) {
         int hv[2];
         HIPCHK(c, hipMemcpyAsync(hv, &d_state[n - 1].hsync, sizeof(hv), hipMemcpyDeviceToHost, c->stream));
@@ -1525,45 +1592,25 @@ int crthip_seq_weave(crthip_ctx *c, const crthip_params *p, int n, void *d_out, 
     if (!d_out || n > c->cap_fields || (p->blend && patch_only)) return CRTHIP_E_ARG;
     if ((rc = check_out(c, p, d_out, ostride, d_out_init, 0))) return rc;
     HIPCHK(c, hipSetDevice(c->device));
-    SeqScratch sc;
-    rc = seq_scratch(c, n, p->outh, &sc);
+    SetsScratch sc;
+    rc = seq_carve(c, 0, n, p->outh, &sc);
     if (rc) return rc;
+    if (!patch_only && (rc = seq_row_tables(c, p, 0, n, sc))) return rc;      /* (a revisit finds sc.latest as the first visit left it) */
     const int outh = p->outh;
     const size_t pitch = (size_t) p->outw * p->out_bpp;
     const unsigned alpha = out_alpha_mask(p);
-    const int ph = phosphor_mode(p);
-    if (p->blend) {
-        HIPCHK(c, hipMemsetAsync(sc.latest, 0xff, sizeof(int) * (size_t) n * outh, c->stream));       /* -1 everywhere */
-        hipLaunchKernelGGL(k_seq_rowsrc, dim3((n * c->sd.lines + 255) / 256), dim3(256), 0, c->stream, n, c->sd.lines, outh, c->d_lines, sc.latest);
-        for (int k = 0; k < n; k++) {
-            if (ph == PH_FADE)
-                hipLaunchKernelGGL(k_seq_blend_step<PH_FADE>, dim3((unsigned) outh), dim3(256), 0, c->stream, k, outh, pitch,
-                                   (unsigned char *) d_out, ostride, (const unsigned char *) d_out_init, sc.latest, alpha);
-            else if (ph == PH_CLEAR)
-                hipLaunchKernelGGL(k_seq_blend_step<PH_CLEAR>, dim3((unsigned) outh), dim3(256), 0, c->stream, k, outh, pitch,
-                                   (unsigned char *) d_out, ostride, (const unsigned char *) d_out_init, sc.latest, alpha);
-            else
-                hipLaunchKernelGGL(k_seq_blend_step<PH_KEEP>, dim3((unsigned) outh), dim3(256), 0, c->stream, k, outh, pitch,
-                                   (unsigned char *) d_out, ostride, (const unsigned char *) d_out_init, sc.latest, alpha);
+    unsigned char *out = (unsigned char *) d_out;
+    const unsigned char *init = (const unsigned char *) d_out_init;
+    dispatch_phosphor(phosphor_mode(p), [&](auto ph) {
+        constexpr int PH = decltype(ph)::value;
+        if (p->blend) {
+            for (int k = 0; k < n; k++)
+                hipLaunchKernelGGL(k_seq_blend_step<PH>, dim3((unsigned) outh), dim3(256), 0, c->stream, k, outh, pitch, out, ostride, init, sc.latest, alpha);
+        } else {
+            hipLaunchKernelGGL(k_seq_weave<PH>, dim3((unsigned) n * (unsigned) outh), dim3(256), 0, c->stream, n, outh, pitch, out, ostride, init,
+                               sc.latest, patch_only, alpha);
         }
-        HIPCHK(c, hipGetLastError());
-        return CRTHIP_OK;
-    }
-    if (!patch_only) {
-        HIPCHK(c, hipMemsetAsync(sc.owner, 0, (size_t) n * outh, c->stream));
-        hipLaunchKernelGGL(k_seq_rows, dim3((n * c->sd.lines + 255) / 256), dim3(256), 0, c->stream, n, c->sd.lines, outh, c->d_lines, sc.owner);
-        hipLaunchKernelGGL(k_seq_latest, dim3((outh + 63) / 64), dim3(64), 0, c->stream, n, outh, sc.owner, sc.latest);
-    }
-    const dim3 grid((unsigned) n * (unsigned) outh);
-    if (ph == PH_FADE)
-        hipLaunchKernelGGL(k_seq_weave<PH_FADE>, grid, dim3(256), 0, c->stream, n, outh, pitch,
-                           (unsigned char *) d_out, ostride, (const unsigned char *) d_out_init, sc.latest, patch_only, alpha);
-    else if (ph == PH_CLEAR)
-        hipLaunchKernelGGL(k_seq_weave<PH_CLEAR>, grid, dim3(256), 0, c->stream, n, outh, pitch,
-                           (unsigned char *) d_out, ostride, (const unsigned char *) d_out_init, sc.latest, patch_only, alpha);
-    else
-        hipLaunchKernelGGL(k_seq_weave<PH_KEEP>, grid, dim3(256), 0, c->stream, n, outh, pitch,
-                           (unsigned char *) d_out, ostride, (const unsigned char *) d_out_init, sc.latest, patch_only, alpha);
+    });
     HIPCHK(c, hipGetLastError());
     return CRTHIP_OK;
 }
@@ -1699,33 +1746,6 @@ int crthip_sequence_knobs(crthip_ctx *c, const crthip_params *p, int n, const vo
     return rc;
 }
 
-/* scratch of crthip_sequence_sets (the same lazily grown block as seq_scratch): set_first[n_sets + 1], tab[n] (first field of my
- * set, my set), inc[n_sets] (incoming hsync, vsync, rn), then guess / changed / owner / latest for n fields */
-static int sets_scratch(crthip_ctx *c, int n_sets, int n, int outh, SetsScratch *sc)
-{
-    const auto up = [](size_t v) { return (v + 255) & ~(size_t) 255; };
-    const size_t o_tab = up(sizeof(int) * ((size_t) n_sets + 1)), o_inc = o_tab + up(sizeof(int2) * (size_t) n);
-    const size_t o_guess = o_inc + up(sizeof(int4) * (size_t) n_sets), o_changed = o_guess + up(sizeof(int2) * (size_t) n);
-    const size_t o_owner = o_changed + 256, o_latest = o_owner + up((size_t) n * outh);
-    const size_t need = o_latest + up(sizeof(int) * (size_t) n * outh);
-    if (need > c->seq_cap) {
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (c->d_seq) hipFree(c->d_seq);
-        c->d_seq = 0; c->seq_cap = 0;
-        if (hipMalloc((void **) &c->d_seq, need) != hipSuccess) return set_err(c, CRTHIP_E_NOMEM, "hipMalloc sequence scratch", hipSuccess);
-        c->seq_cap = need;
-    }
-    c->seq_guess_n = 0;                                 /* whatever crthip_seq_sync left in this block is gone */
-    sc->set_first = (int *) c->d_seq;
-    sc->tab = (int2 *) (c->d_seq + o_tab);
-    sc->inc = (int4 *) (c->d_seq + o_inc);
-    sc->guess = (int2 *) (c->d_seq + o_guess);
-    sc->changed = (int *) (c->d_seq + o_changed);
-    sc->owner = c->d_seq + o_owner;
-    sc->latest = (int *) (c->d_seq + o_latest);
-    return CRTHIP_OK;
-}
-
 /* crthip_sequence_sets, and crthip_sequence_sets_knobs when d_recs is given: the call then runs on the library's copy of the blob
  * (knobs_blob over all n fields: record k belongs to field k of the batch, whatever its set) with c->knob_recs set by the caller */
 static int sequence_sets_body(crthip_ctx *c, const crthip_params *p, int n_sets, const int *set_first,
@@ -1772,7 +1792,7 @@ static int sequence_sets_body(crthip_ctx *c, const crthip_params *p, int n_sets,
         if (rc) return rc;
     }
     SetsScratch sc;
-    rc = sets_scratch(c, n_sets, n, p->outh, &sc);
+    rc = seq_carve(c, n_sets, n, p->outh, &sc);
     if (rc) return rc;
     /* the set table: built here, uploaded once (the host copy belongs to the context: it outlives the copy) */
     const size_t tab_ints = (size_t) n_sets + 1, host_ints = ((tab_ints + 63) & ~(size_t) 63) + 2 * (size_t) n;
@@ -1797,67 +1817,35 @@ static int sequence_sets_body(crthip_ctx *c, const crthip_params *p, int n_sets,
     const dim3 gn((n + 63) / 64), gs((n_sets + 63) / 64), b64(64);
     hipLaunchKernelGGL(k_sets_incoming, gs, b64, 0, c->stream, n_sets, sc.set_first, d_state, sc.inc);
     if (streams) {
-        /* as seq_encode_body for the single set: the chains ahead of everything else (k_vhs_chain<SETS>: one wave per set, hist[k] =
-         * the generator at the start of field k, the aberration heights drawn in-stream if asked), clean encode, rand() noise
-         * (which also leaves rn and the histories after every field) */
+        /* every set's chain ahead of everything else (k_vhs_chain<SETS>: one wave per set, hist[k] = the generator at the start of
+         * field k, the aberration heights drawn in-stream if asked; the rand() noise then leaves rn and the histories after every field) */
         hipLaunchKernelGGL(k_sets_guess, gn, b64, 0, c->stream, n, sc.tab, sc.inc, sc.guess);
         rc = crt_run_vhs_chain(c, n, d_state, (p->flags & CRTHIP_F_VHS_DRAW_ABERRATION) != 0, n_sets, sc.set_first);
         if (rc) return rc;
-        crthip_params clean = *p;
-        clean.noise = 0;
-        rc = crt_run_encoder(c, &clean, n, d_images, istride, c->d_analog, d_state, true, 1, false);
-        if (rc) return rc;
-        rc = crt_run_noise(c, p, n, c->d_analog, c->d_inp, d_state, false);
-        if (rc) return rc;
     } else {
         hipLaunchKernelGGL(k_sets_rn, gn, b64, 0, c->stream, n, d_state, sc.tab, sc.inc, sc.guess, c->whole_field);
-        rc = crt_run_encoder(c, p, n, d_images, istride, c->d_inp, d_state, true, 1, false);
-        if (rc) return rc;
     }
-    /* the joint fixed point: one flag for all sets; after pass j the first j fields of every set are final */
-    int passes = 0;
-    crthip_params q = c->knob_recs ? *p : with_signal_envelope(p);
-    if (c->knob_recs) q.loskip_wave_max = c->knob_loskip;
-    for (;;) {
-        passes++;
-        HIPCHK(c, hipMemsetAsync(sc.changed, 0, sizeof(int), c->stream));
+    rc = seq_signal(c, p, n, d_images, istride, d_state, streams);
+    if (rc) return rc;
+    /* the joint fixed point: one flag for all sets */
+    rc = seq_converge(c, p, n, d_state, sc, max_len + 1, "crthip_sequence_sets: the sync chain over the fields did not converge", passes_out,
+                      [&] {
         hipLaunchKernelGGL(k_sets_load, gn, b64, 0, c->stream, n, d_state, sc.tab, sc.inc, sc.guess);
-        rc = crt_run_encoder_state(c, p, n, d_state);
-        if (rc) return rc;
-        rc = crt_run_sync(c, &q, n, c->d_inp, d_state, c->d_lines, 0);
-        if (rc) return rc;
-        hipLaunchKernelGGL(k_seq_compare, gn, b64, 0, c->stream, n, d_state, sc.guess, sc.changed);
-        int flag = 0;
-        HIPCHK(c, hipMemcpyAsync(&flag, sc.changed, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (!flag) break;
-        if (passes > max_len + 1)
-            return set_err(c, CRTHIP_E_HIP, "crthip_sequence_sets: the sync chain over the fields did not converge", hipSuccess);
-    }
-    if (passes_out) *passes_out = passes;
+    });
+    if (rc) return rc;
     if (!streams) crt_run_advance_rn(c, n, d_state);
     crthip_params pb = *p;
     pb.blend = 0;
     rc = crt_run_decode(c, &pb, n, c->d_inp, c->d_lines, d_out, ostride);
     if (rc) return rc;
-    const int outh = p->outh;
-    if (p->blend) {
-        HIPCHK(c, hipMemsetAsync(sc.latest, 0xff, sizeof(int) * (size_t) n * outh, c->stream));       /* -1 everywhere */
-        hipLaunchKernelGGL(k_seq_rowsrc, dim3((n * c->sd.lines + 255) / 256), dim3(256), 0, c->stream, n, c->sd.lines, outh, c->d_lines, sc.latest);
-    } else {
-        HIPCHK(c, hipMemsetAsync(sc.owner, 0, (size_t) n * outh, c->stream));
-        hipLaunchKernelGGL(k_seq_rows, dim3((n * c->sd.lines + 255) / 256), dim3(256), 0, c->stream, n, c->sd.lines, outh, c->d_lines, sc.owner);
-        hipLaunchKernelGGL(k_sets_latest, dim3((n_sets * outh + 63) / 64), dim3(64), 0, c->stream, n_sets, outh, sc.set_first, sc.owner, sc.latest);
-    }
-    const int ph = phosphor_mode(p);
-    unsigned char *out = (unsigned char *) d_out;
-    const unsigned char *init = (const unsigned char *) d_out_init;
-    if (ph == PH_FADE) launch_sets_weave<PH_FADE>(c, p, n_sets, n, max_len, out, ostride, init, out_init_stride, sc);
-    else if (ph == PH_CLEAR) launch_sets_weave<PH_CLEAR>(c, p, n_sets, n, max_len, out, ostride, init, out_init_stride, sc);
-    else launch_sets_weave<PH_KEEP>(c, p, n_sets, n, max_len, out, ostride, init, out_init_stride, sc);
+    rc = seq_row_tables(c, p, n_sets, n, sc);
+    if (rc) return rc;
+    dispatch_phosphor(phosphor_mode(p), [&](auto ph) {
+        launch_sets_weave<decltype(ph)::value>(c, p, n_sets, n, max_len, (unsigned char *) d_out, ostride, (const unsigned char *) d_out_init,
+                                               out_init_stride, sc);
+    });
     HIPCHK(c, hipGetLastError());
-    c->last_lay.pitch = c->sd.hres; c->last_lay.shift = 0; c->last_lay.padv = 0; c->last_lay.wrap = 0; c->last_lay.fstride = c->fstride;
-    c->last_n = n;
+    seq_record_layout(c, n);
     return CRTHIP_OK;
 }
 
