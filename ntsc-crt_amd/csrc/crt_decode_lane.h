@@ -307,7 +307,10 @@ __device__ __forceinline__ unsigned unpack_selector(int format)
  * its own tier -- two copies of the line loop in one kernel, chosen once per wave -- so that a field-pass launches two decoder
  * kernels where it launched four, three of which usually had nothing to do (5 us each in a 230 us step). */
 #ifndef DEC_IN_TILE_DW
-#define DEC_IN_TILE_DW 16                  /* (A/B builds: -DDEC_IN_TILE_DW=8 -DDEC_WAVES_PER_EU=5, profiles/r06_decode_occupancy.txt) */
+#define DEC_IN_TILE_DW 16                  /* (A/B builds: -DDEC_IN_TILE_DW=8 -DDEC_WAVES_PER_EU=5, profiles/r06_decode_occupancy.txt;
+                                              with the row tables in registers that build is the faster one for the float-stage kernel
+                                              at 640x480 -- profiles/ab_decoder_lds_room.txt --, but the switches act on every
+                                              instantiation: DESIGN.md 5.7) */
 #endif
 #ifdef DEC_WAVES_PER_EU
 #define DEC_OCCUPANCY_ATTR __attribute__((amdgpu_waves_per_eu(DEC_WAVES_PER_EU, DEC_WAVES_PER_EU)))
@@ -361,8 +364,6 @@ k_decode(const crthip_params P, int n_fields, const signed char *__restrict__ in
     constexpr int PX_TILE = PXT, PX_PIECES = PXT / 4;
     using TPX = TileRows<PXT>;
     __shared__ unsigned s_px[TPX::DWORDS];
-    __shared__ unsigned long long s_src[64], s_dst[64];
-    __shared__ int s_nrows[64];
 
     const int lane = threadIdx.x;
     int gid = block_item(blockIdx.x, order_k, order_per) * 64 + lane;     /* workgroup order: crt_dev.h */
@@ -410,10 +411,11 @@ k_decode(const crthip_params P, int n_fields, const signed char *__restrict__ in
     const bool act = nrows > 0;
     constexpr int bpp = BPP3 ? 3 : 4;
     const size_t pitch = (size_t) P.outw * bpp;
-    s_src[lane] = (unsigned long long) (inp + (size_t) f * fstride + (act ? lp.pos : 0));
-    s_dst[lane] = (unsigned long long) (outp + (size_t) f * ostride + (size_t) (act ? lp.beg : 0) * pitch);
-    s_nrows[lane] = nrows;
-    wave_lds_fence();
+    /* Row tables.  A lane fills and drains the tiles for the same few rows all line long: it fetches their source pointer, destination
+     * pointer and row count ONCE, here, from the lanes that own the rows (lane_u64 / lane_i32, crt_dev.h: the whole wave is here) and
+     * keeps them in registers, its piece's offset folded in -- no table in LDS, no table read per tile. */
+    const unsigned long long my_src = (unsigned long long) (inp + (size_t) f * fstride + (act ? lp.pos : 0));
+    const unsigned long long my_dst = (unsigned long long) (outp + (size_t) f * ostride + (size_t) (act ? lp.beg : 0) * pitch);
 
     /* tiers 0 and 1 multiply by the carriers scaled by 2^7 (eq_step64_yiq) */
     constexpr int WSCALE = TIER <= 1 ? 128 : 1;
@@ -478,10 +480,31 @@ k_decode(const crthip_params P, int n_fields, const signed char *__restrict__ in
     const int in_row = lane / IN_PIECES, in_piece = lane % IN_PIECES;
     constexpr int IN_ROWS = 64 / IN_PIECES;            /* rows covered by one load instruction */
     const int t0 = xq0 / IN_TILE_DW;               /* bloom: the tiles before the first filtered sample are never read */
+    unsigned long long in_src[IN_PIECES];            /* piece in_piece of rows i * IN_ROWS + in_row */
+#pragma unroll
+    for (int i = 0; i < IN_PIECES; i++) in_src[i] = lane_u64(my_src, i * IN_ROWS + in_row) + in_piece * 16;
+    /* 4-byte formats: 16-byte piece `piece` of rows i * (64 / PX_PIECES) + orow_, kept all line long by the float-stage kernels
+     * (3 registers per row; 96 in all for the 16-pixel tile).  The integer stages hold their state in register pairs and have no
+     * room for that at 4 waves per SIMD (133 registers, or 128 and scratch), and the 3-byte drain walks PX_TILE rows per lane: both
+     * fetch per drain (below) */
+    constexpr bool PX_KEEP = FSTAGE && !BPP3;
+    const int orow_ = lane / PX_PIECES, piece = lane % PX_PIECES;
+    unsigned long long px_dst[PX_KEEP ? PX_PIECES : 1];
+    int px_nr[PX_KEEP ? PX_PIECES : 1];
+    if (PX_KEEP) {
+#pragma unroll
+        for (int i = 0; i < PX_PIECES; i++) {
+            px_dst[i] = lane_u64(my_dst, i * (64 / PX_PIECES) + orow_) + piece * 16;
+            px_nr[i] = lane_i32(nrows, i * (64 / PX_PIECES) + orow_);
+        }
+    }
+    /* where this lane's next pixel goes in its row of the pixel tile, in bytes: + 4 per pixel, back to the row's start at the drain */
+    const unsigned px_row0 = (unsigned) TPX::row(lane) * 4;
+    unsigned px_cur = px_row0;
     v4i stage[IN_PIECES];
 #pragma unroll
     for (int i = 0; i < IN_PIECES; i++) {
-        stage[i] = gload16u(s_src[i * IN_ROWS + in_row] + t0 * (IN_TILE_DW * 4) + in_piece * 16);
+        stage[i] = gload16u(in_src[i] + t0 * (IN_TILE_DW * 4));
     }
     constexpr int NQ = (S::AV_LEN + 3) / 4;        /* dwords per line window; the last one may run past
                                                       AV_LEN: the filters are causal, the extra samples feed nothing */
@@ -498,7 +521,7 @@ k_decode(const crthip_params P, int n_fields, const signed char *__restrict__ in
         if (t + 1 < NT) {
 #pragma unroll
             for (int i = 0; i < IN_PIECES; i++) {
-                stage[i] = gload16u(s_src[i * IN_ROWS + in_row] + (t + 1) * (IN_TILE_DW * 4) + in_piece * 16);
+                stage[i] = gload16u(in_src[i] + (t + 1) * (IN_TILE_DW * 4));
             }
         }
         const int xq_end = (t + 1) * IN_TILE_DW < NQ ? (t + 1) * IN_TILE_DW : NQ;
@@ -605,7 +628,8 @@ k_decode(const crthip_params P, int n_fields, const signed char *__restrict__ in
                         r = clampi(r, 0, 255); g = clampi(g, 0, 255); b = clampi(b, 0, 255);
                         rgb = lshl_or(lshl_or((unsigned) r, 8, (unsigned) g), 8, (unsigned) b);
                     }
-                    s_px[TPX::row(lane) + (px - px0)] = rgb;
+                    *(unsigned *) ((char *) s_px + px_cur) = rgb;
+                    px_cur += 4;
                     ppos += dx;
                     px++;
                     if (px == tile_end) {
@@ -613,14 +637,15 @@ k_decode(const crthip_params P, int n_fields, const signed char *__restrict__ in
                         const int cnt = px - px0;
                         wave_lds_fence();
                         if (!BPP3) {
-                            const int orow_ = lane / PX_PIECES, piece = lane % PX_PIECES;  /* 4 pixels = 16 bytes per piece */
-                            const int have = cnt - piece * 4;                      /* pixels of this piece that exist */
-#pragma unroll 2
+                            const int have = cnt - piece * 4;                      /* pixels of this piece (4 pixels = 16 bytes) that exist */
+#pragma unroll
                             for (int i = 0; i < PX_PIECES; i++) {
                                 const int rr_ = i * (64 / PX_PIECES) + orow_;
-                                const int nr = s_nrows[rr_];
+                                /* (the whole wave is here -- the drain is wave-uniform --, so the fetch may stand in front of the branch) */
+                                const int nr = PX_KEEP ? px_nr[PX_KEEP ? i : 0] : lane_i32(nrows, rr_);
+                                const unsigned long long d_row = PX_KEEP ? px_dst[PX_KEEP ? i : 0] : lane_u64(my_dst, rr_) + piece * 16;
                                 if (nr > 0 && have > 0) {
-                                    const unsigned long long d = s_dst[rr_] + (size_t) (px0 + piece * 4) * 4;
+                                    const unsigned long long d = d_row + (size_t) px0 * 4;
                                     const unsigned *sp = s_px + TPX::row(rr_) + piece * 4;
                                     unsigned v[4] = { sp[0], sp[1], sp[2], sp[3] };
                                     if (blend) {
@@ -662,9 +687,10 @@ k_decode(const crthip_params P, int n_fields, const signed char *__restrict__ in
                             const int half = lane / PX_TILE, c = lane % PX_TILE;
                             for (int i = 0; i < PX_TILE; i++) {
                                 const int rr_ = i * (64 / PX_TILE) + half;
-                                const int nr = s_nrows[rr_];
+                                const int nr = lane_i32(nrows, rr_);                /* (the whole wave is here: the drain is wave-uniform) */
+                                const unsigned long long d_row = lane_u64(my_dst, rr_);
                                 if (nr > 0 && c < cnt) {
-                                    const unsigned long long d = s_dst[rr_] + (size_t) (px0 + c) * 3;
+                                    const unsigned long long d = d_row + (size_t) (px0 + c) * 3;
                                     int rgb3 = (int) s_px[TPX::row(rr_) + c];
                                     if (blend) {
                                         const int o0 = (int) gload8(d), o1 = (int) gload8(d + 1), o2 = (int) gload8(d + 2);
@@ -681,6 +707,7 @@ k_decode(const crthip_params P, int n_fields, const signed char *__restrict__ in
                             }
                         }
                         wave_lds_fence();
+                        px_cur = px_row0;
                         px0 = px;
                         tile_end = px0 + PX_TILE < outw ? px0 + PX_TILE : outw;
                     }

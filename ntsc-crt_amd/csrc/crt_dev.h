@@ -283,6 +283,18 @@ __device__ __forceinline__ void wave_lds_fence()
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
+/* Lane src_lane's value of v, for every lane its own src_lane: ds_bpermute_b32, the LDS crossbar without LDS memory.  What a lane keeps
+ * per ROW of a 64-row tile (row pointers, row counts) stays in the registers of the row's lane and travels this way to the lanes that
+ * serve the row cooperatively -- no table in LDS.  Every lane that is read from must be active: call it where the whole wave is. */
+__device__ __forceinline__ int lane_i32(int v, int src_lane) { return __builtin_amdgcn_ds_bpermute(src_lane << 2, v); }
+__device__ __forceinline__ unsigned long long lane_u64(unsigned long long v, int src_lane)
+{
+    const int a = src_lane << 2;
+    const unsigned lo = (unsigned) __builtin_amdgcn_ds_bpermute(a, (int) (unsigned) v);
+    const unsigned hi = (unsigned) __builtin_amdgcn_ds_bpermute(a, (int) (unsigned) (v >> 32));
+    return ((unsigned long long) hi << 32) | lo;
+}
+
 __device__ __forceinline__ int posmod(int x, int n) { return ((x % n) + n) % n; }  /* crt_core.c:17 */
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 

@@ -211,14 +211,8 @@ struct RowTiles {
     }
     /* (r6) the row pointers of the 64 rows live in their lanes' registers and travel by ds_bpermute_b32 (the LDS crossbar, no LDS
      * memory) where rounds 1-5 kept two 64-entry tables in LDS: 1 KB less per wave -- 12 672 instead of 13 696 B for the 16-dword
-     * image / 32-dword sample tile pair, i.e. 12 instead of 11 waves per CU (all lanes are active wherever this is called) */
-    __device__ __forceinline__ unsigned long long lane_u64(unsigned long long v, int src_lane) const
-    {
-        const int a = src_lane << 2;
-        const unsigned lo = (unsigned) __builtin_amdgcn_ds_bpermute(a, (int) (unsigned) v);
-        const unsigned hi = (unsigned) __builtin_amdgcn_ds_bpermute(a, (int) (unsigned) (v >> 32));
-        return ((unsigned long long) hi << 32) | lo;
-    }
+     * image / 32-dword sample tile pair, i.e. 12 instead of 11 waves per CU (lane_u64: crt_dev.h; all lanes are active wherever it is
+     * called here) */
     __device__ __forceinline__ int piece_offset(int tile) const
     {
         const int off = tile * (TILE * 4) + piece * 16;
