@@ -267,6 +267,7 @@ int  crthip_reserve(crthip_ctx *ctx, int n_fields);
  *   d_state    : n crthip_state, 144 bytes apart, 4-byte aligned; exactly the n records of the call are read and written.
  *   d_lines    : n * CRT_LINES crthip_line, 32 bytes apart, 4-byte aligned.
  *   d_recs     : n crthip_knob_rec, 32 bytes apart, 4-byte aligned, READ ONLY.
+ *   d_levs     : n crthip_level_rec (crthip_bind_levels), 16 bytes apart, 4-byte aligned, READ ONLY; checked when it is bound.
  *   d_hist     : n x 32 words (crthip_vhs_bind_history), 4-byte aligned; checked when it is bound.
  *   d_analog, d_inp, d_inp_flat : n fields crthip_field_stride() bytes apart, 4-byte aligned; ALL crthip_field_stride() bytes of a
  *              field belong to the library (CRT_INPUT_SIZE samples, the CRTHIP_TAIL mirror, slack the 16-byte pieces of the
@@ -340,6 +341,35 @@ int  crthip_fieldpass(crthip_ctx *ctx, const crthip_params *p, int n,
  * launched before there were picture knobs.  An env whose picture words contradict each other (pic neither 0 nor 1, floors
  * outside 0..3 or the smallest above the largest, words set without pic) is refused like a wrong magic.  black_point,
  * white_point and the encoder hue also enter the encoder and stay uniform; CRTHIP_SYSTEM_PV1K stays refused.
+ *
+ * LEVEL KNOBS: black point and white point per field as well -- the keys q / a and w / s of the interactive driver (crt_main.c's
+ * controls) -- the first two knobs that reach the ENCODER's arithmetic: crt_modulate computes
+ * ire = (BLACK_LEVEL + black_point) + (((y + i + q) * white) >> 10) with white = WHITE_LEVEL * white_point / 100
+ * (crt_ntsc.c:311-318 and its siblings), and the black point enters the decoder once more through bright (crt_core.c:305).
+ * crthip_knobs_prepare7 takes crthip_knobs7 and gives TWO record arrays: recs / env exactly what crthip_knobs_prepare5 gives, except
+ * that every field's bright and tier_floor (and with them env->tier_floors and env->bright_abs_lo) come from THAT field's black
+ * point -- env->pic == 1 --, and levs[k] = { white, ire_base } exactly as crthip_params_finalize derives crthip_params.white and
+ * .ire_base, with lenv = their largest magnitudes over the batch.  env->loskip_wave_max is the bound for the widest signal range any
+ * field's (white, ire_base, noise) gives.  p->black_point, p->white_point, p->white and p->ire_base are then ignored.  It refuses what
+ * crthip_knobs_prepare5 refuses (and a NULL levs / lenv).
+ * crthip_bind_levels hands the level records to the context: d_levs = the n records, uploaded by the caller (DEVICE memory, read
+ * when the kernels run, as d_recs), lenv copied; (NULL, NULL) unbinds.  The six knob entry points read the binding --
+ * crthip_fieldpass_knobs, crthip_sequence_knobs, crthip_sequence_sets_knobs, and crthip_seq_encode / _sync / _decode after
+ * crthip_seq_bind_knobs; level record k belongs to the field knob record k belongs to -- and each then requires lenv->n == n and an
+ * env with pic == 1.  (crthip_knobs_env.pic cannot say it: pic == 2 is refused by contract.)  The encoder then runs its LV
+ * instantiations, which load white and ire_base per lane from the record of the lane's field -- a wavefront's 64 rows may belong to
+ * two fields -- and chooses between the 24-bit and the exact kernels by lenv->white_abs_max / ire_base_abs_max (both below 2^13 for
+ * the 24-bit ones) in place of p->white / p->ire_base: ONE field over the bound sends the whole call to the exact instantiation,
+ * with identical samples.  The uniform entry points and crthip_stills behave exactly as before whether or not something is bound, and
+ * so does a knob call while nothing is bound.  Everything crthip_fieldpass_knobs accepts is accepted with the same meaning (both
+ * chroma patterns, both VHS noise models, SNES, template, NES-RGB, bloom, FIR, the phosphor flags, blend, both kernel shapes and
+ * signal layouts, overlap chunks, graph capture: records rewritten between replays must stay inside the captured lenv; records
+ * outside it give unspecified samples but no access outside a buffer -- the levels only enter arithmetic).
+ * REFUSED (CRTHIP_E_ARG, crthip_error_string says why, nothing launched, d_out and d_state untouched): a lenv whose magic or n does
+ * not match; d_levs off its 4-byte alignment; CRTHIP_SYSTEM_PV1K (as for every knob); CRTHIP_SYSTEM_NES, whose samples come from the
+ * 512 x 12 table built for ONE (black, white) pair; CRTHIP_F_NES_BORDER, whose border colour is baked into the cached skeleton with
+ * one pair.  The encoder hue stays uniform: it changes the burst and with it the cached skeleton variants and the margin kernels;
+ * crthip_knobs7.reserved is kept for it and ignored today.
  */
 typedef struct crthip_knobs     { int noise, mon_hue, saturation, reserved; } crthip_knobs;                                /* 16 bytes */
 typedef struct crthip_knobs5    { int noise, mon_hue, saturation, brightness, contrast, reserved[3]; } crthip_knobs5;      /* 32 bytes */
@@ -353,6 +383,13 @@ int  crthip_fieldpass_knobs(crthip_ctx *ctx, const crthip_params *p, int n,
                             const void *d_images, size_t image_stride, void *d_out, size_t out_stride,
                             crthip_state *d_state,
                             const crthip_knob_rec *d_recs /* n, DEVICE */, const crthip_knobs_env *env /* host */);
+typedef struct crthip_knobs7    { int noise, mon_hue, saturation, brightness, contrast, black_point, white_point, reserved; } crthip_knobs7;   /* 32 bytes */
+typedef struct crthip_level_rec { int white, ire_base, reserved[2]; } crthip_level_rec;                                    /* 16 bytes */
+typedef struct crthip_levels_env { int magic, n, white_abs_max, ire_base_abs_max, reserved[4]; } crthip_levels_env;
+int  crthip_knobs_prepare7(const crthip_params *p, int n, const crthip_knobs7 *knobs,
+                           crthip_knob_rec *recs /* n, host, out */, crthip_level_rec *levs /* n, host, out */,
+                           crthip_knobs_env *env, crthip_levels_env *lenv);
+int  crthip_bind_levels(crthip_ctx *ctx, const crthip_level_rec *d_levs /* n, DEVICE */, const crthip_levels_env *lenv /* host, copied */);
 
 /*
  * SEQUENCE mode: n consecutive fields of ONE television set -- what the reference's

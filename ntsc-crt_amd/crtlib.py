@@ -103,6 +103,27 @@ class KnobsEnv(C.Structure):
 KNOB_REC_INTS = C.sizeof(KnobRec) // 4
 
 
+class Knobs7(C.Structure):
+    """crthip_knobs7 (include/crt_hip.h): the five knobs and the two that reach the encoder, black point and white point."""
+    _fields_ = [("noise", C.c_int), ("mon_hue", C.c_int), ("saturation", C.c_int), ("brightness", C.c_int),
+                ("contrast", C.c_int), ("black_point", C.c_int), ("white_point", C.c_int), ("reserved", C.c_int)]
+
+
+class LevelRec(C.Structure):
+    """crthip_level_rec (include/crt_hip.h): what the encoder's LV kernels read per field, 16 bytes."""
+    _fields_ = [("white", C.c_int), ("ire_base", C.c_int), ("reserved", C.c_int * 2)]
+
+
+class LevelsEnv(C.Structure):
+    """crthip_levels_env (include/crt_hip.h): the batch-wide bounds of the level records of one crthip_knobs_prepare7 call."""
+    _fields_ = [("magic", C.c_int), ("n", C.c_int), ("white_abs_max", C.c_int), ("ire_base_abs_max", C.c_int),
+                ("reserved", C.c_int * 4)]
+
+
+LEVEL_REC_INTS = C.sizeof(LevelRec) // 4
+LEV_WHITE, LEV_IRE_BASE = 0, 1                           # columns of the (n, 4) level record array
+
+
 class Params(C.Structure):
     """crthip_params (include/crt_hip.h)."""
     _fields_ = [(n, C.c_int) for n in (
@@ -223,6 +244,10 @@ def load_library():
         L.crthip_sequence_knobs.argtypes = [vp, PP, ci, vp, sz, vp, sz, vp, vp, vp, C.POINTER(KnobsEnv), C.POINTER(ci)]
         L.crthip_sequence_sets_knobs.argtypes = [vp, PP, ci, C.POINTER(ci), vp, sz, vp, sz, vp, sz, vp, vp, C.POINTER(KnobsEnv), C.POINTER(ci)]
         L.crthip_seq_bind_knobs.argtypes = [vp, vp, C.POINTER(KnobsEnv)]
+    if hasattr(L, "crthip_knobs_prepare7"):                       # (likewise)
+        L.crthip_knobs_prepare7.argtypes = [PP, ci, C.POINTER(Knobs7), C.POINTER(KnobRec), C.POINTER(LevelRec),
+                                            C.POINTER(KnobsEnv), C.POINTER(LevelsEnv)]
+        L.crthip_bind_levels.argtypes = [vp, vp, C.POINTER(LevelsEnv)]
     _LIB = L
     return L
 
@@ -263,14 +288,21 @@ def knobs_prepare(params, knobs):
     """crthip_knobs_prepare / crthip_knobs_prepare5 (host only): ``knobs`` = (n, 3) integers, one (noise, mon_hue, saturation) per
     field, or (n, 5): (noise, mon_hue, saturation, brightness, contrast) -- the picture knobs as well --, for the finalized
     ``params`` -> (records as an (n, 8) int32 numpy array in the layout of KnobRec, KnobsEnv).  Every knob entry point of CRT takes
-    either width."""
+    either width.  (n, 7): (..., black_point, white_point) as well -- crthip_knobs_prepare7; the KnobsEnv then carries the encoder's
+    level records and their bounds as ``env.levs`` ((n, 4) int32, the layout of LevelRec) and ``env.lenv`` (knobs_prepare7 returns
+    all four), which CRT.upload_knobs uploads and binds."""
     import numpy as np
     if hasattr(knobs, "detach"):
         knobs = knobs.detach().cpu().numpy()
     k = np.asarray(knobs)
+    if k.ndim == 2 and k.shape[1] == 7 and k.shape[0] >= 1 and np.issubdtype(k.dtype, np.integer):
+        recs, levs, env, lenv = knobs_prepare7(params, k)
+        env.levs, env.lenv = levs, lenv
+        return recs, env
     if k.ndim != 2 or k.shape[1] not in (3, 5) or k.shape[0] < 1 or not np.issubdtype(k.dtype, np.integer):
-        raise ValueError("knobs must be an (n, 3) integer array of (noise, mon_hue, saturation) "
-                         "or an (n, 5) one of (noise, mon_hue, saturation, brightness, contrast)")
+        raise ValueError("knobs must be an (n, 3) integer array of (noise, mon_hue, saturation), "
+                         "an (n, 5) one of (noise, mon_hue, saturation, brightness, contrast) "
+                         "or an (n, 7) one of (noise, mon_hue, saturation, brightness, contrast, black_point, white_point)")
     n, five = int(k.shape[0]), k.shape[1] == 5
     kin = np.zeros((n, 8 if five else 4), dtype=np.int32)
     kin[:, :k.shape[1]] = k
@@ -285,6 +317,30 @@ def knobs_prepare(params, knobs):
     if rc:
         raise ValueError("crthip_knobs_prepare%s failed (%d)" % ("5" if five else "", rc))
     return recs, env
+
+
+def knobs_prepare7(params, knobs):
+    """crthip_knobs_prepare7 (host only): ``knobs`` = (n, 7) integers, one (noise, mon_hue, saturation, brightness, contrast,
+    black_point, white_point) per field -> (knob records (n, 8) int32, level records (n, 4) int32, KnobsEnv, LevelsEnv)."""
+    import numpy as np
+    if hasattr(knobs, "detach"):
+        knobs = knobs.detach().cpu().numpy()
+    k = np.asarray(knobs)
+    if k.ndim != 2 or k.shape[1] != 7 or k.shape[0] < 1 or not np.issubdtype(k.dtype, np.integer):
+        raise ValueError("knobs must be an (n, 7) integer array of (noise, mon_hue, saturation, brightness, contrast, "
+                         "black_point, white_point)")
+    n = int(k.shape[0])
+    kin = np.zeros((n, 8), dtype=np.int32)
+    kin[:, :7] = k
+    recs = np.zeros((n, KNOB_REC_INTS), dtype=np.int32)
+    levs = np.zeros((n, LEVEL_REC_INTS), dtype=np.int32)
+    env, lenv = KnobsEnv(), LevelsEnv()
+    rc = load_library().crthip_knobs_prepare7(C.byref(params), n, kin.ctypes.data_as(C.POINTER(Knobs7)),
+                                              recs.ctypes.data_as(C.POINTER(KnobRec)), levs.ctypes.data_as(C.POINTER(LevelRec)),
+                                              C.byref(env), C.byref(lenv))
+    if rc:
+        raise ValueError("crthip_knobs_prepare7 failed (%d)" % rc)
+    return recs, levs, env, lenv
 
 
 def stills_schedule(interlaced=True, first_field=0, frames=4):
@@ -360,6 +416,8 @@ class CRT:
         self._settings = None
         self.knob_recs = None      # device records of fieldpass_knobs ([n, 8] int32, allocated by the first upload_knobs) and their bounds
         self._knob_env = None
+        self.level_recs = None     # device level records of an (n, 7) upload_knobs ([n, 4] int32), bound to the context while in use
+        self._levels_bound = False
         self.use_stream(None)
         self.vhs_hist = None
         if self.sysid == SYSTEM_VHS:
@@ -510,7 +568,10 @@ class CRT:
 
     def upload_knobs(self, knobs, params):
         """knobs_prepare for ``params`` + one copy into this CRT's device record buffer (allocated once, then reused: a captured
-        fieldpass_knobs reads what the buffer holds at replay).  Returns the KnobsEnv, which fieldpass_knobs(s, None) reuses."""
+        fieldpass_knobs reads what the buffer holds at replay).  Returns the KnobsEnv, which fieldpass_knobs(s, None) reuses.
+        An (n, 7) array -- (..., black_point, white_point), which then replace this CRT's own -- also uploads the encoder's level
+        records into ``level_recs`` and binds them (crthip_bind_levels) for every knob entry point of this object; a following
+        (n, 3) / (n, 5) upload unbinds them."""
         torch = self.torch
         recs, env = knobs_prepare(params, knobs)
         if recs.shape[0] != self.n:
@@ -519,6 +580,19 @@ class CRT:
             self.knob_recs = torch.zeros((self.n, KNOB_REC_INTS), dtype=torch.int32, device=self.dev)
         self.knob_recs.copy_(torch.from_numpy(recs))
         self._knob_env = env
+        # (n, 7): the encoder's level records into their own device buffer (allocated once, like knob_recs), bound to the context
+        # for every knob entry point; a following (n, 3) / (n, 5) upload unbinds them
+        levs = getattr(env, "levs", None)
+        if levs is not None:
+            if self.level_recs is None:
+                self.level_recs = torch.zeros((self.n, LEVEL_REC_INTS), dtype=torch.int32, device=self.dev)
+            self.level_recs.copy_(torch.from_numpy(levs))
+            self._check(self.L.crthip_bind_levels(self.ctx, C.c_void_p(self.level_recs.data_ptr()), C.byref(env.lenv)),
+                        "crthip_bind_levels")
+            self._levels_bound = True
+        elif self._levels_bound:
+            self._check(self.L.crthip_bind_levels(self.ctx, None, None), "crthip_bind_levels")
+            self._levels_bound = False
         return env
 
     def fieldpass_knobs(self, s, knobs, params=None):

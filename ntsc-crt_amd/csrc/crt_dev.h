@@ -455,6 +455,27 @@ __device__ __forceinline__ const crthip_knob_rec *knob_blob_recs(const crthip_pa
     return (const crthip_knob_rec *) (((unsigned long long) (unsigned) P.reserved[1] << 32) | (unsigned) P.reserved[0]);
 }
 
+/* Level knobs (crthip_knobs_prepare7, crthip_bind_levels): black point and white point per field.  The active-video kernels have a
+ * further instantiation, LV, that takes white and ire_base from the field's crthip_level_rec.  Again no signature changes: in the
+ * library's copy of the blob of such a call the words `white` and `ire_base` -- which the LV kernels do not read as values, and the
+ * launch code replaces by the bounds of crthip_levels_env (crthip_ctx.lev_*) -- carry the device pointer to the level record of the
+ * launch's field 0, as `reserved` carries the knob records'.  crthip_ctx.lev_on says that such a call is under way (level_call). */
+static_assert(offsetof(crthip_params, ire_base) == offsetof(crthip_params, white) + sizeof(int), "white and ire_base are neighbours: one device pointer");
+static inline void level_blob_set(crthip_params *q, const crthip_level_rec *d_levs)
+{
+    static_assert(2 * sizeof(int) == sizeof(d_levs), "a device pointer fits crthip_params.white + .ire_base");
+    memcpy(&q->white, &d_levs, sizeof(int));
+    memcpy(&q->ire_base, (const char *) &d_levs + sizeof(int), sizeof(int));
+}
+static inline const crthip_level_rec *level_blob_get(const crthip_params *q)
+{
+    return (const crthip_level_rec *) (((unsigned long long) (unsigned) q->ire_base << 32) | (unsigned) q->white);
+}
+__device__ __forceinline__ const crthip_level_rec *level_blob_recs(const crthip_params &P)
+{
+    return (const crthip_level_rec *) (((unsigned long long) (unsigned) P.ire_base << 32) | (unsigned) P.white);
+}
+
 /* Picture knobs (crthip_knobs_prepare5): is a call with such records under way?  The decoders then launch their PK instantiations */
 static inline bool knob_pic_call(const crthip_ctx *c);
 /* the tier flags a field's floor (crthip_knob_rec.tier_floor: 0, 2 or 3) puts on each of its lines -- what the decoders (and, min_tier >= 4,
@@ -624,6 +645,9 @@ struct crthip_ctx {
     int knob_floor_lo;          /* ... and the smallest tier floor of its fields: what decoder_min_tier starts from then */
     const crthip_knob_rec *seq_knob_recs;   /* crthip_seq_bind_knobs: the shard's records for crthip_seq_encode / _sync / _decode (nullptr: none bound) */
     crthip_knobs_env seq_knob_env;          /* ... and the library's copy of their bounds */
+    const crthip_level_rec *lev_recs;       /* crthip_bind_levels: the caller's device level records for the knob entry points (nullptr: none bound) */
+    crthip_levels_env lev_env;              /* ... and the library's copy of their bounds */
+    int lev_on;                             /* the knob call under way (knob_recs != nullptr) runs with them: the encoder launches its LV instantiations */
     hipStream_t aux_stream;
     hipEvent_t ev_fork, ev_join, ev_chunk[CRTHIP_MAX_CHUNKS];
     hipEvent_t ev_mfork, ev_mjoin;   /* the margin kernel beside the active-video kernel (crt_encode.hip, launch_encoder) */
@@ -637,6 +661,7 @@ struct crthip_ctx {
 };
 
 static inline bool knob_pic_call(const crthip_ctx *c) { return c->knob_recs != nullptr && c->knob_pic != 0; }
+static inline bool level_call(const crthip_ctx *c) { return c->knob_recs != nullptr && c->lev_on != 0; }
 
 static inline int set_err(crthip_ctx *c, int code, const char *what, hipError_t e)
 {

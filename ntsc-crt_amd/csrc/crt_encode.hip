@@ -427,7 +427,10 @@ template <class S> __device__ __forceinline__ int source_row(const crthip_params
  * 64-byte pieces at the reference's odd line starts are its dearest part */
 /* KN: the noise gain is the one of the lane's field (crthip_knob_rec, crt_dev.h) -- one more per-lane load beside state[f], and a
  * vector register where the uniform instantiations multiply by a scalar one */
-template <class S, bool NOISE, bool FAST, bool IN4, bool CLAMP, int ACT, int OT = 16, int OL = OT, bool KN = false>
+/* LV: white and ire_base are the ones of the lane's field (crthip_level_rec, crt_dev.h) -- one more per-lane load beside state[f] and
+ * the noise gain, and vector operands where the uniform instantiations multiply by / add scalar ones.  The 64 rows of a wave may
+ * belong to two fields: nothing below takes either value for wave-uniform */
+template <class S, bool NOISE, bool FAST, bool IN4, bool CLAMP, int ACT, int OT = 16, int OL = OT, bool KN = false, bool LV = false>
 __global__ void __launch_bounds__(64)
 k_active(const crthip_params P, int n_fields, const unsigned char *__restrict__ images, size_t istride,
          signed char *__restrict__ dst, size_t fstride, const crthip_state *__restrict__ state,
@@ -515,7 +518,8 @@ k_active(const crthip_params P, int n_fields, const unsigned char *__restrict__ 
             for (int k = 0; k < 5; k++) { s_cc5[lane * CC5_STRIDE + 2 * k] = cI[k]; s_cc5[lane * CC5_STRIDE + 2 * k + 1] = cQ[k]; }
         }
         const int cy_ = P.iir_c[0], ci_ = P.iir_c[1], cq_ = P.iir_c[2];
-        const int white = P.white, ire_base = P.ire_base;
+        int white = P.white, ire_base = P.ire_base;
+        if constexpr (LV) { const crthip_level_rec lv = level_blob_recs(P)[f]; white = lv.white; ire_base = lv.ire_base; }
         int hy = 0, hi = 0, hq = 0;
         const bool hipass = (P.flags & CRTHIP_F_HIPASS) != 0;
         int cph = 0;                                              /* x % CCS for the 5-sample system (wave-uniform) */
@@ -647,7 +651,7 @@ k_active(const crthip_params P, int n_fields, const unsigned char *__restrict__ 
                         const int nz = KN ? mad24_vvv(nb, noise256, neg_noise127_256) : mad24_vv(nb, noise256, neg_noise127_256);
                         __builtin_amdgcn_sched_barrier(0);
                         const int miq = add_hiwords(pI, pQ);
-                        ire = mad24_vv(oy + miq, white64, ire_base_65536);
+                        ire = LV ? mad24_vvv(oy + miq, white64, ire_base_65536) : mad24_vv(oy + miq, white64, ire_base_65536);
                         ire = clampi(ire, 0, (110 << 16) | 0xffff);
                         ire = add_hiwords(ire, nz);
                         ire = clampi(ire, -127, 127);
@@ -664,8 +668,8 @@ k_active(const crthip_params P, int n_fields, const unsigned char *__restrict__ 
                         /* (r6) with noise to add, the >> 10 is not taken at all: white and the base scaled by another 2^6 leave the
                          * level in the HIGH word, the clamp to [0, 110] works on the scaled value (monotone: same result), and the
                          * noise add below takes the high words of both its operands (|white| < 2^17, host-checked) */
-                        if (NOISE) ire = mad24_vv(oy + miq, white64, ire_base_65536);
-                        else ire = mad24_vv(oy + miq, white, ire_base_1024) >> 10;
+                        if (NOISE) ire = LV ? mad24_vvv(oy + miq, white64, ire_base_65536) : mad24_vv(oy + miq, white64, ire_base_65536);
+                        else ire = (LV ? mad24_vvv(oy + miq, white, ire_base_1024) : mad24_vv(oy + miq, white, ire_base_1024)) >> 10;
                     } else {
                         const int mi = (oi * ccI) >> 4;
                         const int mq = (oq * ccQ) >> 4;
@@ -710,7 +714,7 @@ k_active(const crthip_params P, int n_fields, const unsigned char *__restrict__ 
  *   C  modulate, scale, clamp, + noise, pack: fully parallel, a lane takes 4 consecutive samples (one dword store)
  * so a field is 30 waves and the serial chain per wave is 753 x 4 instructions.  Same arithmetic, exact 32-bit
  * multiplies throughout.  RGB-input systems only (the NES's table encoder is cheap as it is). */
-template <class S, bool NOISE, bool CLAMP, bool KN = false>
+template <class S, bool NOISE, bool CLAMP, bool KN = false, bool LV = false>
 __global__ void __launch_bounds__(64)
 k_active_row(const crthip_params P, int n_fields, const unsigned char *__restrict__ images, size_t istride,
              signed char *__restrict__ dst, size_t fstride, const crthip_state *__restrict__ state,
@@ -744,6 +748,7 @@ k_active_row(const crthip_params P, int n_fields, const unsigned char *__restric
     const int c_rp = lane >> 4, c_j = lane & 15;
     int c_live[CP], c_start[CP], c_cI[CP][CCS], c_cQ[CP][CCS];
     int c_noise[CP];                                     /* the noise gain of the pass's row: the batch's, or (KN) its field's */
+    int c_white[CP], c_base[CP];                         /* LV: white and ire_base of the pass's row (its field's crthip_level_rec) */
     unsigned c_rn0[CP];
     unsigned long long c_dst[CP];
 #pragma unroll
@@ -757,6 +762,8 @@ k_active_row(const crthip_params P, int n_fields, const unsigned char *__restric
         c_rn0[ps] = (unsigned) st.rn;
         c_noise[ps] = P.noise;
         if constexpr (KN) c_noise[ps] = knob_blob_recs(P)[f].noise;
+        c_white[ps] = 0; c_base[ps] = 0;
+        if constexpr (LV) { const crthip_level_rec lv = level_blob_recs(P)[f]; c_white[ps] = lv.white; c_base[ps] = lv.ire_base; }
         const int crow = carrier_row<S>(y + P.yo, st.field, st.frame, st.aux);
 #pragma unroll
         for (int k = 0; k < CCS; k++) { c_cI[ps][k] = P.modI[crow][k]; c_cQ[ps][k] = P.modQ[crow][k]; }
@@ -771,7 +778,7 @@ k_active_row(const crthip_params P, int n_fields, const unsigned char *__restric
         const int sy = source_row<S>(P, y, field);
         a_src[r] = (unsigned long long) (images + (size_t) f * istride + (size_t) sy * w * in_bpp);
     }
-    const int white = P.white, ire_base = P.ire_base;
+    const int white = LV ? 0 : P.white, ire_base = LV ? 0 : P.ire_base;      /* (LV: the two words of the blob carry the records' pointer) */
 
     for (int t0 = 0; t0 < destw; t0 += TS) {
         /* ---- A: fetch + convert, lane = sample t0 + lane of every row ---- */
@@ -836,7 +843,7 @@ k_active_row(const crthip_params P, int n_fields, const unsigned char *__restric
 #pragma unroll
                 for (int m = 1; m < CCS; m++) if (ph == m) { ccI = c_cI[ps][m]; ccQ = c_cQ[ps][m]; }
                 const int mi = (hi * ccI) >> 4, mq = (hq * ccQ) >> 4;
-                int ire = ire_base + (((hy + mi + mq) * white) >> 10);
+                int ire = LV ? c_base[ps] + (((hy + mi + mq) * c_white[ps]) >> 10) : ire_base + (((hy + mi + mq) * white) >> 10);
                 ire = clampi(ire, 0, 110);
                 if (NOISE) { rn = lcg_step(rn); ire = noisy(ire, rn, c_noise[ps]); }
                 else if (CLAMP) ire = clampi(ire, -127, 127);
@@ -1209,11 +1216,14 @@ k_margin_pad(const crthip_params P, int n_fields, signed char *__restrict__ dst,
 }
 
 template <class S>
-static bool encoder_fast_ok(const crthip_params *p)
+static bool encoder_fast_ok(const crthip_ctx *c, const crthip_params *p)
 {
-    const int wh = p->white < 0 ? -p->white : p->white;
+    /* a call with level records (crthip_bind_levels): the batch's largest |white| and |ire_base| decide -- one field over the bound
+     * sends the whole call to the exact kernels (p->white / p->ire_base carry the records' pointer then, crt_dev.h) */
+    const bool lv = level_call(c);
+    const int wh = lv ? c->lev_env.white_abs_max : p->white < 0 ? -p->white : p->white;
     const int nz = p->noise < 0 ? -p->noise : p->noise;
-    const int ib = p->ire_base < 0 ? -p->ire_base : p->ire_base;
+    const int ib = lv ? c->lev_env.ire_base_abs_max : p->ire_base < 0 ? -p->ire_base : p->ire_base;
     /* noise * 256 is a 24-bit multiplier in k_active; (y + i + q) * white * 64 + (ire_base << 16) must not wrap: |y + i + q| <= 1020 +
      * 609 + 534 (8-bit pixels through crt_ntsc.c:307-309, carriers <= 16 / 16), so 2163 * 2^13 * 64 + 2^13 * 2^16 < 2^31.  (Rounds 1-5
      * let white up to 2^23 into the fast kernels, where the product could wrap differently from the reference's; nothing sane is near.) */
@@ -1256,10 +1266,23 @@ static void launch_active(crthip_ctx *c, const crthip_params *p, int n, const vo
     }
     const bool noise = FULL && p->noise != 0;
     const bool kn = noise && c->knob_recs;                       /* per-field noise: the KN instantiations (fused path only) */
+    /* per-field black / white point: the LV instantiations -- every shape a knob call reaches below has one, with the per-field noise
+     * (kn: a level call is a knob call) or without any (the batch's largest noise is 0; the clean field of the rand()-noise VHS build
+     * and of CRT_DO_VSYNC 0).  The PPU encoder and the 5-sample system have none: such a call is refused (crt_host.hip, knobs_blob) */
+    constexpr bool LVS = FULL && !S::IS_NES && S::CCS == 4;
+    const bool lv = LVS && level_call(c);
+    (void) lv;
     if constexpr (!S::IS_NES) {
         /* kernel shape (crthip_set_shape): small batches take the scanline-parallel encoder */
         if (c->shape == 2 || (c->shape == 0 && n <= ROWS_SHAPE_MAX_FIELDS_ENC)) {
             const dim3 rgrid((total + 7) / 8);
+            if constexpr (LVS) {
+                if (lv) {
+                    if (kn) hipLaunchKernelGGL((k_active_row<S, true, true, true, true>), rgrid, block, 0, c->stream, *p, n, img, istride, dst, lay.fstride, d_state, c->d_jump16, c->d_jump1, lay.pitch, lay.shift, wrapn);
+                    else hipLaunchKernelGGL((k_active_row<S, false, true, false, true>), rgrid, block, 0, c->stream, *p, n, img, istride, dst, lay.fstride, d_state, c->d_jump16, c->d_jump1, lay.pitch, lay.shift, wrapn);
+                    return;
+                }
+            }
             if constexpr (FULL) {
                 if (kn) {
                     hipLaunchKernelGGL((k_active_row<S, true, true, true>), rgrid, block, 0, c->stream, *p, n, img, istride, dst, lay.fstride, d_state, c->d_jump16, c->d_jump1, lay.pitch, lay.shift, wrapn);
@@ -1301,7 +1324,8 @@ static void launch_active(crthip_ctx *c, const crthip_params *p, int n, const vo
 #define CRTHIP_LAUNCH_ACTIVE_BIG(NZ, ...) \
     do { if (wide_in) hipLaunchKernelGGL((k_active<S, NZ, true, true, true, 32, 64, CRTHIP_ENC_OL64 __VA_ARGS__>), ogrid, block, 0, c->stream, *p, n, img, istride, dst, lay.fstride, d_state, c->d_jump16, bo.K, bo.per, lay.pitch, lay.shift, wrapn); \
          else hipLaunchKernelGGL((k_active<S, NZ, true, true, true, 16, 32, CRTHIP_ENC_OL32 __VA_ARGS__>), ogrid, block, 0, c->stream, *p, n, img, istride, dst, lay.fstride, d_state, c->d_jump16, bo.K, bo.per, lay.pitch, lay.shift, wrapn); } while (0)
-            if (kn) CRTHIP_LAUNCH_ACTIVE_BIG(true, , true);
+            if (lv) { if (kn) CRTHIP_LAUNCH_ACTIVE_BIG(true, , true, true); else CRTHIP_LAUNCH_ACTIVE_BIG(false, , false, true); }
+            else if (kn) CRTHIP_LAUNCH_ACTIVE_BIG(true, , true);
             else if (noise) CRTHIP_LAUNCH_ACTIVE_BIG(true); else CRTHIP_LAUNCH_ACTIVE_BIG(false);
 #undef CRTHIP_LAUNCH_ACTIVE_BIG
             return;
@@ -1310,6 +1334,13 @@ static void launch_active(crthip_ctx *c, const crthip_params *p, int n, const vo
 #define CRTHIP_LAUNCH_ACTIVE(NZ, I4, ...) \
     do { if (wide_in) hipLaunchKernelGGL((k_active<S, NZ, FAST, I4, FULL, 32 __VA_ARGS__>), ogrid, block, 0, c->stream, *p, n, img, istride, dst, lay.fstride, d_state, c->d_jump16, bo.K, bo.per, lay.pitch, lay.shift, wrapn); \
          else hipLaunchKernelGGL((k_active<S, NZ, FAST, I4, FULL, 16 __VA_ARGS__>), ogrid, block, 0, c->stream, *p, n, img, istride, dst, lay.fstride, d_state, c->d_jump16, bo.K, bo.per, lay.pitch, lay.shift, wrapn); } while (0)
+    if constexpr (LVS) {
+        if (lv) {                                                /* (the default tiles spelt out: KN and LV are the last parameters) */
+            if (kn) { if (in4) CRTHIP_LAUNCH_ACTIVE(true, true, , 16, 16, true, true); else CRTHIP_LAUNCH_ACTIVE(true, false, , 16, 16, true, true); }
+            else    { if (in4) CRTHIP_LAUNCH_ACTIVE(false, true, , 16, 16, false, true); else CRTHIP_LAUNCH_ACTIVE(false, false, , 16, 16, false, true); }
+            return;
+        }
+    }
     if constexpr (FULL) {
         if (kn) {                                                /* (the default tiles spelt out: KN is the last parameter) */
             if (in4) CRTHIP_LAUNCH_ACTIVE(true, true, , 16, 16, true); else CRTHIP_LAUNCH_ACTIVE(true, false, , 16, 16, true);
@@ -1374,7 +1405,7 @@ template <class S, bool FULL>
 static void launch_active_any(crthip_ctx *c, const crthip_params *p, int n, const void *d_images, size_t istride,
                               signed char *dst, const crthip_state *d_state, const sig_layout &lay)
 {
-    if (encoder_fast_ok<S>(p) && !c->force_exact) launch_active<S, FULL, true>(c, p, n, d_images, istride, dst, d_state, lay);
+    if (encoder_fast_ok<S>(c, p) && !c->force_exact) launch_active<S, FULL, true>(c, p, n, d_images, istride, dst, d_state, lay);
     else launch_active<S, FULL, false>(c, p, n, d_images, istride, dst, d_state, lay);
 }
 

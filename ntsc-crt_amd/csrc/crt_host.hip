@@ -980,6 +980,7 @@ static int fieldpass_chunk(crthip_ctx *c, const crthip_params *p, int enc, int f
     if (c->knob_recs) {
         pk = *p;
         knob_blob_set(&pk, c->knob_recs + first);
+        if (level_call(c)) level_blob_set(&pk, level_blob_get(p) + first);
         p = &pk;
     }
     if (part & 1) {
@@ -1138,6 +1139,7 @@ static bool knobs_env_pic_ok(const crthip_knobs_env *env)
 
 static int knobs_blob(crthip_ctx *c, const crthip_params *p, int n, const crthip_knob_rec *d_recs, const crthip_knobs_env *env, crthip_params *q)
 {
+    c->lev_on = 0;
     if (!d_recs || !env) return CRTHIP_E_ARG;
     if (CHECK_WORD(c, d_recs)) return CRTHIP_E_ARG;
     if (env->magic != CRTHIP_KNOBS_MAGIC) return set_err(c, CRTHIP_E_ARG, "knobs: env does not come from crthip_knobs_prepare", hipSuccess);
@@ -1148,12 +1150,28 @@ static int knobs_blob(crthip_ctx *c, const crthip_params *p, int n, const crthip
         return set_err(c, CRTHIP_E_ARG, "knobs: the 5-sample decoder (PV-1000) takes monitor hue and saturation from the uniform parameters", hipSuccess);
     if (env->noise_max < 0 || env->sat_abs_max < 0) return set_err(c, CRTHIP_E_ARG, "knobs: env bounds", hipSuccess);
     if (!knobs_env_pic_ok(env)) return set_err(c, CRTHIP_E_ARG, "knobs: the env's picture words contradict each other (not from crthip_knobs_prepare5)", hipSuccess);
+    /* level records bound (crthip_bind_levels): every knob call runs with them -- or is refused here, before anything is launched */
+    if (c->lev_recs) {
+        if (c->lev_env.n != n) return set_err(c, CRTHIP_E_ARG, "levels: the bound crthip_levels_env was prepared for another number of fields", hipSuccess);
+        if (env->pic != 1)
+            return set_err(c, CRTHIP_E_ARG, "levels: bound level records go with the records of crthip_knobs_prepare7 (env->pic == 1: bright per field)", hipSuccess);
+        if (p->flags & CRTHIP_F_NES_BORDER)
+            return set_err(c, CRTHIP_E_ARG, "levels: CRTHIP_F_NES_BORDER bakes the border colour into the cached skeleton with ONE (black point, white point) pair", hipSuccess);
+        if (c->system == CRTHIP_SYSTEM_NES)
+            return set_err(c, CRTHIP_E_ARG, "levels: the NES encoder's samples come from a 512 x 12 table built for ONE (black point, white point) pair", hipSuccess);
+    }
     c->knob_pic = env->pic;
     c->knob_floor_lo = env->pic ? (env->tier_floors & 0xff) : 0;
     *q = *p;
     q->noise = env->noise_max;
     q->saturation = env->sat_abs_max;
     knob_blob_set(q, d_recs);
+    if (c->lev_recs) {
+        /* the LV kernels read white / ire_base from the records; the blob's two words carry the pointer to them (crt_dev.h), and
+         * the launch code decides by c->lev_env where it read them (encoder_fast_ok) */
+        level_blob_set(q, c->lev_recs);
+        c->lev_on = 1;
+    }
     c->knob_loskip = env->loskip_wave_max < LOSKIP_WAVE_MAX ? LOSKIP_WAVE_MAX : env->loskip_wave_max > T0_WAVE_MAX ? T0_WAVE_MAX : env->loskip_wave_max;
     return CRTHIP_OK;
 }
@@ -1663,6 +1681,21 @@ int crthip_seq_bind_knobs(crthip_ctx *c, const crthip_knob_rec *d_recs, const cr
     if (!knobs_env_pic_ok(env)) return set_err(c, CRTHIP_E_ARG, "knobs: the env's picture words contradict each other (not from crthip_knobs_prepare5)", hipSuccess);
     c->seq_knob_recs = d_recs;
     c->seq_knob_env = *env;
+    return CRTHIP_OK;
+}
+
+/* The encoder's level records for the knob entry points (crt_hip.h, LEVEL KNOBS): kept until unbound; checked against each call's n,
+ * env and system by knobs_blob.  Nothing is copied or launched here. */
+int crthip_bind_levels(crthip_ctx *c, const crthip_level_rec *d_levs, const crthip_levels_env *lenv)
+{
+    if (!c) return CRTHIP_E_ARG;
+    if (!d_levs && !lenv) { c->lev_recs = nullptr; return CRTHIP_OK; }
+    if (!d_levs || !lenv) return set_err(c, CRTHIP_E_ARG, "crthip_bind_levels: records and env go together ((NULL, NULL) unbinds)", hipSuccess);
+    if (check_word(c, d_levs, "d_levs needs 4-byte alignment")) return CRTHIP_E_ARG;
+    if (lenv->magic != CRTHIP_LEVELS_MAGIC) return set_err(c, CRTHIP_E_ARG, "levels: lenv does not come from crthip_knobs_prepare7", hipSuccess);
+    if (lenv->n <= 0 || lenv->white_abs_max < 0 || lenv->ire_base_abs_max < 0) return set_err(c, CRTHIP_E_ARG, "levels: lenv bounds", hipSuccess);
+    c->lev_recs = d_levs;
+    c->lev_env = *lenv;
     return CRTHIP_OK;
 }
 

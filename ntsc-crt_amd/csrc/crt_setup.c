@@ -706,14 +706,18 @@ abs_sat(int v)
  * bound of the batch is the smaller of the bounds at the smallest and the largest noise.
  */
 /* kn: the caller's knobs as ints, `stride` apart: noise, mon_hue, saturation and -- pic: crthip_knobs5 -- brightness, contrast */
+/* levs != 0 (crthip_knobs_prepare7): two more ints per field, black_point and white_point -- the field's bright and tier floor come
+ * from ITS black point, levs[k] = the encoder's pair as crthip_params_finalize derives it, lenv = the batch's largest magnitudes */
 static int
-knobs_prepare_any(const crthip_params *p, int n, const int *kn, int stride, int pic, crthip_knob_rec *recs, crthip_knobs_env *env)
+knobs_prepare_any(const crthip_params *p, int n, const int *kn, int stride, int pic, crthip_knob_rec *recs, crthip_knobs_env *env,
+                  crthip_level_rec *levs, crthip_levels_env *lenv)
 {
     struct crt_sysdef d;
     crthip_params q;
     int k, sn, cs, lo, hi, bound, b2;
     int noise_lo, noise_hi, noise_abs = 0, sat_abs = 0;
     int floor_lo = 3, floor_hi = 0, bright_abs = 0;
+    int white_abs = 0, base_abs = 0;
 
     if (p == 0 || kn == 0 || recs == 0 || env == 0 || n <= 0 || p->finalized != CRTHIP_PARAMS_MAGIC ||
         crt_sysdef_get(&d, p->system, p->chroma_pattern) != CRTHIP_OK) {
@@ -738,7 +742,8 @@ knobs_prepare_any(const crthip_params *p, int n, const int *kn, int stride, int 
         if (pic) {
             /* the decoder's two: the luma offset as crthip_params_finalize derives it (crt_core.c:305), the contrast as it is, and
              * the tier they ask of the field's lines (k_hsync_wave turns it into the lines' tier flags) */
-            const int bright = kk[3] - (d.black_level + p->black_point);
+            const int black_point = levs ? kk[5] : p->black_point;
+            const int bright = kk[3] - (d.black_level + black_point);
             const int fl = crt_setup_decoder_floor(p, bright, kk[4]);
             recs[k].bright = bright;
             recs[k].contrast = kk[4];
@@ -747,18 +752,41 @@ knobs_prepare_any(const crthip_params *p, int n, const int *kn, int stride, int 
             if (fl > floor_hi) floor_hi = fl;
             if (fl < 2 && abs_sat(bright) > bright_abs) bright_abs = abs_sat(bright);
         }
+        if (levs) {
+            memset(&levs[k], 0, sizeof(levs[k]));
+            levs[k].white = d.white_level * kk[6] / 100;            /* crt_ntsc.c:318, as crthip_params_finalize */
+            levs[k].ire_base = d.black_level + kk[5];               /* crt_ntsc.c:311 */
+            if (abs_sat(levs[k].white) > white_abs) white_abs = abs_sat(levs[k].white);
+            if (abs_sat(levs[k].ire_base) > base_abs) base_abs = abs_sat(levs[k].ire_base);
+        }
         if (noise < noise_lo) noise_lo = noise;
         if (noise > noise_hi) noise_hi = noise;
         if (abs_sat(noise) > noise_abs) noise_abs = abs_sat(noise);
         if (abs_sat(kk[2]) > sat_abs) sat_abs = abs_sat(kk[2]);
     }
+    /* The signal range of a field: sync level ... white level + noise term (crt_setup_signal_range).  The RGB encoders clamp the level
+     * to 0 .. 110 whatever white and ire_base are (crt_ntsc.c:319-320), so there one evaluation per noise extreme covers every field;
+     * the PPU encoder's samples depend on the pair itself, so the bound is taken over the fields' pairs (a run of equal pairs once). */
     q = *p;
-    q.noise = noise_lo;
-    crt_setup_signal_range(&q, &lo, &hi);
-    bound = crt_setup_loskip_bound(lo, hi);
-    q.noise = noise_hi;
-    crt_setup_signal_range(&q, &lo, &hi);
-    b2 = crt_setup_loskip_bound(lo, hi);
+    bound = b2 = 0x7fffffff;
+    for (k = 0; k < n; k++) {
+        if (levs) {
+            const int *const kk = kn + (size_t) k * (size_t) stride;
+            if (k > 0 && (!d.ppu_input || (kk[5] == q.black_point && kk[6] == q.white_point))) continue;
+            q.black_point = kk[5];
+            q.white_point = kk[6];
+        } else if (k > 0) {
+            break;
+        }
+        q.noise = noise_lo;
+        crt_setup_signal_range(&q, &lo, &hi);
+        sn = crt_setup_loskip_bound(lo, hi);
+        if (sn < bound) bound = sn;
+        q.noise = noise_hi;
+        crt_setup_signal_range(&q, &lo, &hi);
+        sn = crt_setup_loskip_bound(lo, hi);
+        if (sn < b2) b2 = sn;
+    }
     env->magic = CRTHIP_KNOBS_MAGIC;
     env->n = n;
     env->noise_max = noise_abs;
@@ -769,20 +797,39 @@ knobs_prepare_any(const crthip_params *p, int n, const int *kn, int stride, int 
         env->tier_floors = floor_lo | (floor_hi << 8);
         env->bright_abs_lo = bright_abs;
     }
+    if (levs) {
+        memset(lenv, 0, sizeof(*lenv));
+        lenv->magic = CRTHIP_LEVELS_MAGIC;
+        lenv->n = n;
+        lenv->white_abs_max = white_abs;
+        lenv->ire_base_abs_max = base_abs;
+    }
     return CRTHIP_OK;
 }
 
 int
 crthip_knobs_prepare(const crthip_params *p, int n, const crthip_knobs *knobs, crthip_knob_rec *recs, crthip_knobs_env *env)
 {
-    return knobs_prepare_any(p, n, knobs ? &knobs->noise : 0, (int) (sizeof(*knobs) / sizeof(int)), 0, recs, env);
+    return knobs_prepare_any(p, n, knobs ? &knobs->noise : 0, (int) (sizeof(*knobs) / sizeof(int)), 0, recs, env, 0, 0);
 }
 
 /* The same with brightness and contrast per field: the records' last three words and the env's picture words filled in. */
 int
 crthip_knobs_prepare5(const crthip_params *p, int n, const crthip_knobs5 *knobs, crthip_knob_rec *recs, crthip_knobs_env *env)
 {
-    return knobs_prepare_any(p, n, knobs ? &knobs->noise : 0, (int) (sizeof(*knobs) / sizeof(int)), 1, recs, env);
+    return knobs_prepare_any(p, n, knobs ? &knobs->noise : 0, (int) (sizeof(*knobs) / sizeof(int)), 1, recs, env, 0, 0);
+}
+
+/* The same with black point and white point per field: the picture words from every field's own black point, and the encoder's
+ * level records with their bounds beside them (crthip_bind_levels). */
+int
+crthip_knobs_prepare7(const crthip_params *p, int n, const crthip_knobs7 *knobs, crthip_knob_rec *recs, crthip_level_rec *levs,
+                      crthip_knobs_env *env, crthip_levels_env *lenv)
+{
+    if (levs == 0 || lenv == 0) {
+        return CRTHIP_E_ARG;
+    }
+    return knobs_prepare_any(p, n, knobs ? &knobs->noise : 0, (int) (sizeof(*knobs) / sizeof(int)), 1, recs, env, levs, lenv);
 }
 
 /*

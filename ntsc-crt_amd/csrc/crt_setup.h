@@ -64,6 +64,7 @@ void crt_setup_vhs_power_table(unsigned long first, unsigned long step, int coun
 
 #define CRTHIP_PARAMS_MAGIC 0x43525431            /* "CRT1" */
 #define CRTHIP_KNOBS_MAGIC  0x43524b31            /* "CRK1": crthip_knobs_env of crthip_knobs_prepare */
+#define CRTHIP_LEVELS_MAGIC 0x43524c31            /* "CRL1": crthip_levels_env of crthip_knobs_prepare7 */
 
 /* CRTHIP_F_PHOSPHOR_FADE / _CLEAR (crt_hip.h): fade^CRTHIP_PHOSPHOR_DEPTH(c) == 0 for every byte c, fade^(DEPTH-1)(255) != 0 */
 #define CRTHIP_PHOSPHOR_MASK  (CRTHIP_F_PHOSPHOR_FADE | CRTHIP_F_PHOSPHOR_CLEAR)
