@@ -268,6 +268,7 @@ int  crthip_reserve(crthip_ctx *ctx, int n_fields);
  *   d_lines    : n * CRT_LINES crthip_line, 32 bytes apart, 4-byte aligned.
  *   d_recs     : n crthip_knob_rec, 32 bytes apart, 4-byte aligned, READ ONLY.
  *   d_levs     : n crthip_level_rec (crthip_bind_levels), 16 bytes apart, 4-byte aligned, READ ONLY; checked when it is bound.
+ *   d_hues     : n crthip_hue_rec (crthip_bind_hues), 640 bytes apart, 4-byte aligned, READ ONLY; checked when it is bound.
  *   d_hist     : n x 32 words (crthip_vhs_bind_history), 4-byte aligned; checked when it is bound.
  *   d_analog, d_inp, d_inp_flat : n fields crthip_field_stride() bytes apart, 4-byte aligned; ALL crthip_field_stride() bytes of a
  *              field belong to the library (CRT_INPUT_SIZE samples, the CRTHIP_TAIL mirror, slack the 16-byte pieces of the
@@ -340,7 +341,7 @@ int  crthip_fieldpass(crthip_ctx *ctx, const crthip_params *p, int n,
  * Records of crthip_knobs_prepare keep those words and env words 0, and a call with them launches exactly the kernels it
  * launched before there were picture knobs.  An env whose picture words contradict each other (pic neither 0 nor 1, floors
  * outside 0..3 or the smallest above the largest, words set without pic) is refused like a wrong magic.  black_point,
- * white_point and the encoder hue also enter the encoder and stay uniform; CRTHIP_SYSTEM_PV1K stays refused.
+ * white_point and the encoder hue also enter the encoder and stay uniform here (LEVEL KNOBS and HUE KNOB below); CRTHIP_SYSTEM_PV1K stays refused.
  *
  * LEVEL KNOBS: black point and white point per field as well -- the keys q / a and w / s of the interactive driver (crt_main.c's
  * controls) -- the first two knobs that reach the ENCODER's arithmetic: crt_modulate computes
@@ -368,8 +369,31 @@ int  crthip_fieldpass(crthip_ctx *ctx, const crthip_params *p, int n,
  * REFUSED (CRTHIP_E_ARG, crthip_error_string says why, nothing launched, d_out and d_state untouched): a lenv whose magic or n does
  * not match; d_levs off its 4-byte alignment; CRTHIP_SYSTEM_PV1K (as for every knob); CRTHIP_SYSTEM_NES, whose samples come from the
  * 512 x 12 table built for ONE (black, white) pair; CRTHIP_F_NES_BORDER, whose border colour is baked into the cached skeleton with
- * one pair.  The encoder hue stays uniform: it changes the burst and with it the cached skeleton variants and the margin kernels;
- * crthip_knobs7.reserved is kept for it and ignored today.
+ * one pair.  crthip_knobs7.reserved is ignored; the encoder hue per field is crthip_knobs8.hue, below.
+ *
+ * HUE KNOB: the ENCODER hue per field as well -- keys 5 / 6 of the interactive driver, NTSC_SETTINGS.hue, the "color artifacting
+ * hue" -- the last of the values the viewer turns between two fields that are numbers.  It rotates the three carrier tables burst,
+ * modI and modQ (crt_ntsc.c:174-183 and its siblings), which enter the active-video arithmetic, the burst samples of every video
+ * line and the ccf preset.  crthip_knobs_prepare8 takes crthip_knobs8 -- crthip_knobs7 with its last word named hue -- and gives
+ * THREE record arrays: recs / levs / env / lenv exactly what crthip_knobs_prepare7 gives for the first seven values (the signal
+ * range, and with it env->loskip_wave_max, does not move with the hue: the burst stays inside sync level .. white level), and
+ * hues[k] = exactly the three tables crthip_params_finalize derives for a copy of p whose hue is field k's (negative angles
+ * truncate as C's do; NES-RGB rotates only its burst; as_color == 0 gives all zeros), henv = { magic, n }.  p->hue and the three
+ * tables in p are then ignored.  It refuses what crthip_knobs_prepare7 refuses, a NULL hues / henv, CRTHIP_SYSTEM_NES, and a field
+ * whose carriers leave the encoder's 24-bit bound (|modI|, |modQ| < 2048; with sn >> 10 no hue does, and it is checked all the same).
+ * crthip_bind_hues hands the records to the context, as crthip_bind_levels does and independently of it: d_hues = the n records in
+ * DEVICE memory, read when the kernels run, henv copied; (NULL, NULL) unbinds.  The same six knob entry points read the binding and
+ * each then requires henv->n == n; hue record k belongs to the field knob record k belongs to.  With hues bound and levels not,
+ * p->white and p->ire_base apply.  The encoder then runs its HU instantiations: the active-video kernels load the carriers of the
+ * lane's field per lane; the margin kernels still copy the cached skeleton variants -- which a hue call neither rebuilds nor
+ * invalidates: crthip_table_generation does not move -- and recompute the bytes of the burst windows from the field's record before
+ * the noise is added; the ccf preset comes from the record.  The uniform entry points and crthip_stills behave exactly as before
+ * whether or not something is bound.  Graph capture: records rewritten between replays must come from crthip_knobs_prepare8.
+ * REFUSED (CRTHIP_E_ARG, crthip_error_string says why, nothing launched, d_out and d_state untouched): a henv whose magic or n does
+ * not match; d_hues off its 4-byte alignment; CRTHIP_SYSTEM_PV1K (as for every knob); CRTHIP_SYSTEM_NES, whose PPU encoder has no
+ * per-field instantiation (as for the levels).
+ * OUT OF SCOPE: as_color and raw per field (keys SPACE and t), NES and PV-1000, knobs in crthip_stills, knob videos through
+ * shard.py / crt_hip_node.h.
  */
 typedef struct crthip_knobs     { int noise, mon_hue, saturation, reserved; } crthip_knobs;                                /* 16 bytes */
 typedef struct crthip_knobs5    { int noise, mon_hue, saturation, brightness, contrast, reserved[3]; } crthip_knobs5;      /* 32 bytes */
@@ -390,6 +414,19 @@ int  crthip_knobs_prepare7(const crthip_params *p, int n, const crthip_knobs7 *k
                            crthip_knob_rec *recs /* n, host, out */, crthip_level_rec *levs /* n, host, out */,
                            crthip_knobs_env *env, crthip_levels_env *lenv);
 int  crthip_bind_levels(crthip_ctx *ctx, const crthip_level_rec *d_levs /* n, DEVICE */, const crthip_levels_env *lenv /* host, copied */);
+typedef struct crthip_knobs8    { int noise, mon_hue, saturation, brightness, contrast, black_point, white_point, hue; } crthip_knobs8;   /* 32 bytes */
+typedef struct crthip_hue_rec {                                                                                           /* 640 bytes */
+    int burst[CRTHIP_CARRIER_ROWS][CRTHIP_MAX_CCS];
+    int modI[CRTHIP_CARRIER_ROWS][CRTHIP_MAX_CCS];
+    int modQ[CRTHIP_CARRIER_ROWS][CRTHIP_MAX_CCS];
+    int reserved[10];
+} crthip_hue_rec;
+typedef struct crthip_hues_env { int magic, n, reserved[6]; } crthip_hues_env;
+int  crthip_knobs_prepare8(const crthip_params *p, int n, const crthip_knobs8 *knobs,
+                           crthip_knob_rec *recs /* n, host, out */, crthip_level_rec *levs /* n, host, out */,
+                           crthip_hue_rec *hues /* n, host, out */,
+                           crthip_knobs_env *env, crthip_levels_env *lenv, crthip_hues_env *henv);
+int  crthip_bind_hues(crthip_ctx *ctx, const crthip_hue_rec *d_hues /* n, DEVICE */, const crthip_hues_env *henv /* host, copied */);
 
 /*
  * SEQUENCE mode: n consecutive fields of ONE television set -- what the reference's

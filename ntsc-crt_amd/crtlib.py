@@ -120,7 +120,29 @@ class LevelsEnv(C.Structure):
                 ("reserved", C.c_int * 4)]
 
 
+class Knobs8(C.Structure):
+    """crthip_knobs8 (include/crt_hip.h): crthip_knobs7 with its last word named: the ENCODER hue of the field."""
+    _fields_ = [("noise", C.c_int), ("mon_hue", C.c_int), ("saturation", C.c_int), ("brightness", C.c_int),
+                ("contrast", C.c_int), ("black_point", C.c_int), ("white_point", C.c_int), ("hue", C.c_int)]
+
+
+CARRIER_ROWS, MAX_CCS = 10, 5                            # CRTHIP_CARRIER_ROWS, CRTHIP_MAX_CCS
+
+
+class HueRec(C.Structure):
+    """crthip_hue_rec (include/crt_hip.h): the three carrier tables of one field, 640 bytes."""
+    _fields_ = [("burst", (C.c_int * MAX_CCS) * CARRIER_ROWS), ("modI", (C.c_int * MAX_CCS) * CARRIER_ROWS),
+                ("modQ", (C.c_int * MAX_CCS) * CARRIER_ROWS), ("reserved", C.c_int * 10)]
+
+
+class HuesEnv(C.Structure):
+    """crthip_hues_env (include/crt_hip.h)."""
+    _fields_ = [("magic", C.c_int), ("n", C.c_int), ("reserved", C.c_int * 6)]
+
+
 LEVEL_REC_INTS = C.sizeof(LevelRec) // 4
+HUE_REC_INTS = C.sizeof(HueRec) // 4
+HUE_BURST, HUE_MODI, HUE_MODQ = 0, CARRIER_ROWS * MAX_CCS, 2 * CARRIER_ROWS * MAX_CCS    # first column of each table in the (n, 160) array
 LEV_WHITE, LEV_IRE_BASE = 0, 1                           # columns of the (n, 4) level record array
 
 
@@ -248,6 +270,10 @@ def load_library():
         L.crthip_knobs_prepare7.argtypes = [PP, ci, C.POINTER(Knobs7), C.POINTER(KnobRec), C.POINTER(LevelRec),
                                             C.POINTER(KnobsEnv), C.POINTER(LevelsEnv)]
         L.crthip_bind_levels.argtypes = [vp, vp, C.POINTER(LevelsEnv)]
+    if hasattr(L, "crthip_knobs_prepare8"):                       # (likewise)
+        L.crthip_knobs_prepare8.argtypes = [PP, ci, C.POINTER(Knobs8), C.POINTER(KnobRec), C.POINTER(LevelRec), C.POINTER(HueRec),
+                                            C.POINTER(KnobsEnv), C.POINTER(LevelsEnv), C.POINTER(HuesEnv)]
+        L.crthip_bind_hues.argtypes = [vp, vp, C.POINTER(HuesEnv)]
     _LIB = L
     return L
 
@@ -343,6 +369,39 @@ def knobs_prepare7(params, knobs):
     return recs, levs, env, lenv
 
 
+def knobs_prepare8(params, knobs):
+    """crthip_knobs_prepare8 (host only): ``knobs`` = (n, 8) integers, one (noise, mon_hue, saturation, brightness, contrast,
+    black_point, white_point, hue) per field -- hue = the ENCODER hue -> (knob records (n, 8) int32, level records (n, 4) int32,
+    hue records (n, 160) int32 in the layout of HueRec, KnobsEnv, LevelsEnv, HuesEnv).  The KnobsEnv carries ``levs`` / ``lenv`` /
+    ``hues`` / ``henv`` as well: CRT.upload_knobs -- the door of every knob entry point of CRT -- takes the (n, 8) array itself."""
+    import numpy as np
+    if hasattr(knobs, "detach"):
+        knobs = knobs.detach().cpu().numpy()
+    k = np.asarray(knobs)
+    if k.ndim != 2 or k.shape[1] != 8 or k.shape[0] < 1 or not np.issubdtype(k.dtype, np.integer):
+        raise ValueError("knobs must be an (n, 8) integer array of (noise, mon_hue, saturation, brightness, contrast, "
+                         "black_point, white_point, hue)")
+    n = int(k.shape[0])
+    kin = np.ascontiguousarray(k, dtype=np.int32)
+    recs = np.zeros((n, KNOB_REC_INTS), dtype=np.int32)
+    levs = np.zeros((n, LEVEL_REC_INTS), dtype=np.int32)
+    hues = np.zeros((n, HUE_REC_INTS), dtype=np.int32)
+    env, lenv, henv = KnobsEnv(), LevelsEnv(), HuesEnv()
+    rc = load_library().crthip_knobs_prepare8(C.byref(params), n, kin.ctypes.data_as(C.POINTER(Knobs8)),
+                                              recs.ctypes.data_as(C.POINTER(KnobRec)), levs.ctypes.data_as(C.POINTER(LevelRec)),
+                                              hues.ctypes.data_as(C.POINTER(HueRec)), C.byref(env), C.byref(lenv), C.byref(henv))
+    if rc:
+        raise ValueError("crthip_knobs_prepare8 failed (%d)" % rc)
+    env.levs, env.lenv, env.hues, env.henv = levs, lenv, hues, henv
+    return recs, levs, hues, env, lenv, henv
+
+
+def _is_knobs8(knobs):
+    import numpy as np
+    k = knobs.detach().cpu().numpy() if hasattr(knobs, "detach") else np.asarray(knobs)
+    return k.ndim == 2 and k.shape[1] == 8 and k.shape[0] >= 1 and np.issubdtype(k.dtype, np.integer)
+
+
 def stills_schedule(interlaced=True, first_field=0, frames=4):
     """crthip_stills_schedule (host only): the passes of the reference's `ntsc` program (crt_main.c:241-255) as a list of
     (field, frame, aux) -- `frames` passes when progressive, 2 * frames when interlaced; frames = 4 is the CLI."""
@@ -418,6 +477,8 @@ class CRT:
         self._knob_env = None
         self.level_recs = None     # device level records of an (n, 7) upload_knobs ([n, 4] int32), bound to the context while in use
         self._levels_bound = False
+        self.hue_recs = None       # device hue records of an (n, 8) upload_knobs ([n, 160] int32), bound likewise
+        self._hues_bound = False
         self.use_stream(None)
         self.vhs_hist = None
         if self.sysid == SYSTEM_VHS:
@@ -571,9 +632,14 @@ class CRT:
         fieldpass_knobs reads what the buffer holds at replay).  Returns the KnobsEnv, which fieldpass_knobs(s, None) reuses.
         An (n, 7) array -- (..., black_point, white_point), which then replace this CRT's own -- also uploads the encoder's level
         records into ``level_recs`` and binds them (crthip_bind_levels) for every knob entry point of this object; a following
-        (n, 3) / (n, 5) upload unbinds them."""
+        (n, 3) / (n, 5) upload unbinds them.  An (n, 8) array -- (..., hue): the ENCODER hue per field, which then replaces
+        ``params.hue`` -- uploads the hue records into ``hue_recs`` as well and binds both (crthip_bind_hues); a following
+        (n, 3) / (n, 5) / (n, 7) upload unbinds the hues."""
         torch = self.torch
-        recs, env = knobs_prepare(params, knobs)
+        if _is_knobs8(knobs):
+            recs, env = knobs_prepare8(params, knobs)[::3]
+        else:
+            recs, env = knobs_prepare(params, knobs)
         if recs.shape[0] != self.n:
             raise ValueError("%d knob triples for a batch of %d fields" % (recs.shape[0], self.n))
         if self.knob_recs is None:
@@ -593,6 +659,16 @@ class CRT:
         elif self._levels_bound:
             self._check(self.L.crthip_bind_levels(self.ctx, None, None), "crthip_bind_levels")
             self._levels_bound = False
+        hues = getattr(env, "hues", None)
+        if hues is not None:
+            if self.hue_recs is None:
+                self.hue_recs = torch.zeros((self.n, HUE_REC_INTS), dtype=torch.int32, device=self.dev)
+            self.hue_recs.copy_(torch.from_numpy(hues))
+            self._check(self.L.crthip_bind_hues(self.ctx, C.c_void_p(self.hue_recs.data_ptr()), C.byref(env.henv)), "crthip_bind_hues")
+            self._hues_bound = True
+        elif self._hues_bound:
+            self._check(self.L.crthip_bind_hues(self.ctx, None, None), "crthip_bind_hues")
+            self._hues_bound = False
         return env
 
     def fieldpass_knobs(self, s, knobs, params=None):

@@ -476,6 +476,27 @@ __device__ __forceinline__ const crthip_level_rec *level_blob_recs(const crthip_
     return (const crthip_level_rec *) (((unsigned long long) (unsigned) P.ire_base << 32) | (unsigned) P.white);
 }
 
+/* Hue knob (crthip_knobs_prepare8, crthip_bind_hues): the encoder hue per field.  Every kernel that reads the carrier tables on a path
+ * a knob call reaches has a further instantiation, HU, that takes them from the field's crthip_hue_rec.  No signature changes here
+ * either: in the library's copy of the blob of such a call the words burst[0][0] and burst[0][1] -- which the HU kernels do not read
+ * as values -- carry the device pointer to the hue record of the launch's field 0.  crthip_ctx.hue_on says that such a call is under
+ * way (hue_call); crthip_ctx.hue_burst0 keeps the two words the pointer replaced, for the one reader of the blob's own burst table
+ * that remains (the skeleton cache, crt_run_encoder_prepare). */
+static_assert(sizeof(crthip_hue_rec) == 640 && offsetof(crthip_hue_rec, modI) == sizeof(((crthip_params *) 0)->burst), "crthip_hue_rec: the three tables of crthip_params");
+static inline void hue_blob_set(crthip_params *q, const crthip_hue_rec *d_hues)
+{
+    static_assert(2 * sizeof(int) == sizeof(d_hues), "a device pointer fits crthip_params.burst[0][0..1]");
+    memcpy(&q->burst[0][0], &d_hues, 2 * sizeof(int));
+}
+static inline const crthip_hue_rec *hue_blob_get(const crthip_params *q)
+{
+    return (const crthip_hue_rec *) (((unsigned long long) (unsigned) q->burst[0][1] << 32) | (unsigned) q->burst[0][0]);
+}
+__device__ __forceinline__ const crthip_hue_rec *hue_blob_recs(const crthip_params &P)
+{
+    return (const crthip_hue_rec *) (((unsigned long long) (unsigned) P.burst[0][1] << 32) | (unsigned) P.burst[0][0]);
+}
+
 /* Picture knobs (crthip_knobs_prepare5): is a call with such records under way?  The decoders then launch their PK instantiations */
 static inline bool knob_pic_call(const crthip_ctx *c);
 /* the tier flags a field's floor (crthip_knob_rec.tier_floor: 0, 2 or 3) puts on each of its lines -- what the decoders (and, min_tier >= 4,
@@ -648,6 +669,10 @@ struct crthip_ctx {
     const crthip_level_rec *lev_recs;       /* crthip_bind_levels: the caller's device level records for the knob entry points (nullptr: none bound) */
     crthip_levels_env lev_env;              /* ... and the library's copy of their bounds */
     int lev_on;                             /* the knob call under way (knob_recs != nullptr) runs with them: the encoder launches its LV instantiations */
+    const crthip_hue_rec *hue_recs;         /* crthip_bind_hues: the caller's device hue records for the knob entry points (nullptr: none bound) */
+    crthip_hues_env hue_env;                /* ... and the library's copy of their env */
+    int hue_on;                             /* the knob call under way runs with them: the encoder launches its HU instantiations */
+    int hue_burst0[2];                      /* ... and the caller's burst[0][0..1], which the records' pointer replaced in the blob (hue_blob_set) */
     hipStream_t aux_stream;
     hipEvent_t ev_fork, ev_join, ev_chunk[CRTHIP_MAX_CHUNKS];
     hipEvent_t ev_mfork, ev_mjoin;   /* the margin kernel beside the active-video kernel (crt_encode.hip, launch_encoder) */
@@ -662,6 +687,7 @@ struct crthip_ctx {
 
 static inline bool knob_pic_call(const crthip_ctx *c) { return c->knob_recs != nullptr && c->knob_pic != 0; }
 static inline bool level_call(const crthip_ctx *c) { return c->knob_recs != nullptr && c->lev_on != 0; }
+static inline bool hue_call(const crthip_ctx *c) { return c->knob_recs != nullptr && c->hue_on != 0; }
 
 static inline int set_err(crthip_ctx *c, int code, const char *what, hipError_t e)
 {

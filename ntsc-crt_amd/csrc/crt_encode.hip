@@ -1,5 +1,6 @@
 /* crt_encode.hip -- crt_modulate on the GPU: skeleton (M4), active video (M5), ccf preset (M6).  See crt_dev.h. */
 #include "crt_dev.h"
+#include <type_traits>
 
 /* ------------------------------------------------------------------------- */
 /* M4: blanking / sync / burst skeleton                                        */
@@ -29,6 +30,25 @@ __device__ __forceinline__ int ppu_level(int p, int phase)
     return v;
 }
 
+/* Which samples of a field are colour burst -- the one statement of it, shared by skeleton() and the HU margin kernels (which
+ * recompute exactly those bytes from the field's own burst table): the columns CB_BEG .. CB_BEG + CB_LEN of the active lines (NES
+ * timing, crt_nes.c:173-178) or of every line that carries neither equalising pulses nor the vertical sync. */
+template <class S> __device__ __forceinline__ bool equalising_line(int n)
+{
+    return (n >= S::EQU_A_LO && n <= S::EQU_A_HI) || (n >= S::EQU_B_LO && n <= S::EQU_B_HI);
+}
+template <class S> __device__ __forceinline__ bool vsync_line(int n) { return n >= S::VS_LO && n <= S::VS_HI; }
+template <class S> __device__ __forceinline__ bool burst_column(int t)
+{
+    return t >= S::CB_BEG && t < S::CB_BEG + S::CB_LEN && (S::NES_TIMING || t < S::AV_BEG);
+}
+template <class S> __device__ __forceinline__ bool burst_line(const crthip_params &P, int n)
+{
+    if constexpr (S::NES_TIMING) return n >= P.yo && n < P.yo + S::LINES;
+    else return !equalising_line<S>(n) && !vsync_line<S>(n);
+}
+template <class S> __device__ __forceinline__ int burst_sample(int cb) { return (int) (signed char) ((S::BLANK + cb * S::BURST) >> 5); }
+
 /* value of skeleton sample (line n, column t) and whether crt_modulate writes it.
  * RGB systems: crt_ntsc.c:205-252 (+ crt_ntscvhs.c:234-238), crt_snes.c:203-243, crt_template.c, crt_pv1k.c:190-231;
  * NES timing: crt_nes.c:81-104,173-178, crt_nesrgb.c:24-46,104-109 */
@@ -42,9 +62,8 @@ skeleton(const crthip_params &P, int n, int t, int field, int frame, int aux, bo
         bool written = nes_setup;
         val = S::BLANK;
         if (t >= S::SYNC_BEG && t < (n >= 259 ? S::VS_SEP_END : S::BW_BEG)) val = S::SYNC;
-        if (n >= P.yo && n < P.yo + S::LINES && t >= S::CB_BEG && t < S::CB_BEG + S::CB_LEN) {
-            int cb = P.burst[row][tc];
-            val = (int) (signed char) ((S::BLANK + cb * S::BURST) >> 5);
+        if (burst_line<S>(P, n) && burst_column<S>(t)) {
+            val = burst_sample<S>(P.burst[row][tc]);
             written = true;
         }
         if constexpr (S::IS_NES) {
@@ -64,11 +83,11 @@ skeleton(const crthip_params &P, int n, int t, int field, int frame, int aux, bo
         }
         return written;
     } else {
-        if ((n >= S::EQU_A_LO && n <= S::EQU_A_HI) || (n >= S::EQU_B_LO && n <= S::EQU_B_HI)) {   /* equalising pulses */
+        if (equalising_line<S>(n)) {                   /* equalising pulses */
             val = (t < 4 * S::HRES / 100 || (t >= 50 * S::HRES / 100 && t < 54 * S::HRES / 100)) ? S::SYNC : S::BLANK;
             return true;
         }
-        if (n >= S::VS_LO && n <= S::VS_HI) {          /* vertical sync */
+        if (vsync_line<S>(n)) {                        /* vertical sync */
             int a = ((S::VS_BY_FIELD && field == 1) ? 4 : 46) * S::HRES / 100;
             val = (t < a || (t >= 50 * S::HRES / 100 && t < 96 * S::HRES / 100)) ? S::SYNC : S::BLANK;
             return true;
@@ -79,10 +98,7 @@ skeleton(const crthip_params &P, int n, int t, int field, int frame, int aux, bo
         }
         val = S::BLANK;
         if (t >= S::SYNC_BEG && t < S::BW_BEG && (!S::IS_VHS || n < S::VRES - aux)) val = S::SYNC;
-        if (t >= S::CB_BEG && t < S::CB_BEG + S::CB_LEN) {
-            int cb = P.burst[row][tc];
-            val = (int) (signed char) ((S::BLANK + cb * S::BURST) >> 5);
-        }
+        if (burst_column<S>(t)) val = burst_sample<S>(P.burst[row][tc]);     /* (a line that reaches here is a burst_line) */
         return true;
     }
 }
@@ -430,7 +446,9 @@ template <class S> __device__ __forceinline__ int source_row(const crthip_params
 /* LV: white and ire_base are the ones of the lane's field (crthip_level_rec, crt_dev.h) -- one more per-lane load beside state[f] and
  * the noise gain, and vector operands where the uniform instantiations multiply by / add scalar ones.  The 64 rows of a wave may
  * belong to two fields: nothing below takes either value for wave-uniform */
-template <class S, bool NOISE, bool FAST, bool IN4, bool CLAMP, int ACT, int OT = 16, int OL = OT, bool KN = false, bool LV = false>
+/* HU: the carriers are the ones of the lane's field (crthip_hue_rec, crt_dev.h): the eight loads below go to the record where the
+ * uniform instantiations read the blob (scalar loads there, per-lane ones here: crow was per lane already, now f is too) */
+template <class S, bool NOISE, bool FAST, bool IN4, bool CLAMP, int ACT, int OT = 16, int OL = OT, bool KN = false, bool LV = false, bool HU = false>
 __global__ void __launch_bounds__(64)
 k_active(const crthip_params P, int n_fields, const unsigned char *__restrict__ images, size_t istride,
          signed char *__restrict__ dst, size_t fstride, const crthip_state *__restrict__ state,
@@ -509,6 +527,11 @@ k_active(const crthip_params P, int n_fields, const unsigned char *__restrict__ 
         int cI[S::CCS], cQ[S::CCS];
 #pragma unroll
         for (int k = 0; k < S::CCS; k++) { cI[k] = P.modI[crow][k] * (FAST ? 4096 : 1); cQ[k] = P.modQ[crow][k] * (FAST ? 4096 : 1); }
+        if constexpr (HU) {
+            const crthip_hue_rec *hr = hue_blob_recs(P) + f;
+#pragma unroll
+            for (int k = 0; k < S::CCS; k++) { cI[k] = hr->modI[crow][k] * (FAST ? 4096 : 1); cQ[k] = hr->modQ[crow][k] * (FAST ? 4096 : 1); }
+        }
         /* 5 samples per chroma cycle (PV-1000): the carrier phase x % 5 is no compile-time constant of the 4-sample unrolling;
          * the line's five carrier pairs live in LDS, [lane][phase]{I, Q} at an odd row stride */
         constexpr int CC5_STRIDE = 11;
@@ -714,7 +737,7 @@ k_active(const crthip_params P, int n_fields, const unsigned char *__restrict__ 
  *   C  modulate, scale, clamp, + noise, pack: fully parallel, a lane takes 4 consecutive samples (one dword store)
  * so a field is 30 waves and the serial chain per wave is 753 x 4 instructions.  Same arithmetic, exact 32-bit
  * multiplies throughout.  RGB-input systems only (the NES's table encoder is cheap as it is). */
-template <class S, bool NOISE, bool CLAMP, bool KN = false, bool LV = false>
+template <class S, bool NOISE, bool CLAMP, bool KN = false, bool LV = false, bool HU = false>
 __global__ void __launch_bounds__(64)
 k_active_row(const crthip_params P, int n_fields, const unsigned char *__restrict__ images, size_t istride,
              signed char *__restrict__ dst, size_t fstride, const crthip_state *__restrict__ state,
@@ -767,6 +790,11 @@ k_active_row(const crthip_params P, int n_fields, const unsigned char *__restric
         const int crow = carrier_row<S>(y + P.yo, st.field, st.frame, st.aux);
 #pragma unroll
         for (int k = 0; k < CCS; k++) { c_cI[ps][k] = P.modI[crow][k]; c_cQ[ps][k] = P.modQ[crow][k]; }
+        if constexpr (HU) {                              /* the carriers of the row's field (crthip_hue_rec) */
+            const crthip_hue_rec *hr = hue_blob_recs(P) + f;
+#pragma unroll
+            for (int k = 0; k < CCS; k++) { c_cI[ps][k] = hr->modI[crow][k]; c_cQ[ps][k] = hr->modQ[crow][k]; }
+        }
     }
     /* phase A: source row pointers of all R rows (wave-uniform values, computed by every lane) */
     unsigned long long a_src[R];
@@ -1015,7 +1043,36 @@ k_skeleton(const crthip_params P, signed char *__restrict__ skel, size_t fstride
  * end of a line simply continues in the next one) and each lane takes one run of up to 16 samples of it: 16 bytes
  * of the cached skeleton variant (k_skeleton), + noise (LCG state by the 16-step jump table and a 16-entry table
  * for the remainder). */
-template <class S, bool NOISE, bool KN = false>
+/* HU (crthip_bind_hues): the cached variants carry the burst of ONE hue -- a set per distinct hue would cost about 1 MB each -- so a
+ * lane whose 16 samples meet a burst window recomputes those bytes from the burst table of ITS field (crthip_hue_rec), where
+ * skeleton() says they are burst, before the noise is added.  `wds` = the chunk's 16 skeleton bytes, sample (line0, t0) first; the
+ * chunk may run into line0 + 1, whose first 16 columns are never burst.  All other lanes pay the one compare. */
+template <class S>
+__device__ __forceinline__ void hue_patch_burst(const crthip_params &P, const crthip_hue_rec *hr, const crthip_state *st,
+                                                int line0, int t0, int wds[4])
+{
+    static_assert(S::CB_BEG >= 16 && S::CCS == 4, "the samples of a chunk that lie on its second line are no burst columns");
+    if (t0 >= S::CB_BEG + S::CB_LEN || t0 + 16 <= S::CB_BEG || !burst_line<S>(P, line0)) return;
+    const int row = carrier_row<S>(line0, st->field, st->frame, st->aux);
+    const int ph = t0 & 3;                               /* the carrier phase of the chunk's first sample */
+    int b[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) b[j] = hr->burst[row][j];
+    int bb[4];                                           /* the burst sample of sample k: bb[k & 3] */
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        const int cb = ph == 0 ? b[j] : ph == 1 ? b[(j + 1) & 3] : ph == 2 ? b[(j + 2) & 3] : b[(j + 3) & 3];
+        bb[j] = burst_sample<S>(cb) & 0xff;
+    }
+#pragma unroll
+    for (int k = 0; k < 16; k++) {
+        const int t = t0 + k;
+        if (t < S::HRES && burst_column<S>(t))
+            wds[k >> 2] = (wds[k >> 2] & ~(0xff << (8 * (k & 3)))) | (bb[k & 3] << (8 * (k & 3)));
+    }
+}
+
+template <class S, bool NOISE, bool KN = false, bool HU = false>
 __global__ void __launch_bounds__(256)
 k_margin(const crthip_params P, int n_fields, signed char *__restrict__ dst, size_t fstride,
          const crthip_state *__restrict__ state, const uint2 *__restrict__ jump16, const uint2 *__restrict__ jump1,
@@ -1059,6 +1116,10 @@ k_margin(const crthip_params P, int n_fields, signed char *__restrict__ dst, siz
     signed char *out = dst + (size_t) f * fstride;
     const v4i sk = load16u(skel + (size_t) var * fstride + idx0);
     int wds[4] = { sk.x, sk.y, sk.z, sk.w };
+    if constexpr (HU) {
+        const int line0 = idx0 / S::HRES;
+        hue_patch_burst<S>(P, hue_blob_recs(P) + f, st, line0, idx0 - line0 * S::HRES, wds);
+    }
     if constexpr (S::IS_VHS) {
         /* no sync pulse inside the aberration band (crt_ntscvhs.c:234-238): lines n >= VRES - aux */
         const int line0 = idx0 / S::HRES, t0 = idx0 - line0 * S::HRES;
@@ -1127,7 +1188,8 @@ k_margin(const crthip_params P, int n_fields, signed char *__restrict__ dst, siz
  * a0 = wrap for a line whose predecessor carries an active row (the row's last `wrap` samples run into this line: k_active's), else 0.
  * A chunk that lies inside the first PADC columns of line n >= 1 is stored a second time behind line n - 1 (the copy that makes
  * windows over a line end contiguous); chunks that only partly do are not -- `padv` (crt_fused_layout) is what that guarantees. */
-template <class S, bool NOISE, bool KN = false>
+/* HU: as in k_margin; the copy behind the previous line is stored from the same registers and so carries the patched bytes */
+template <class S, bool NOISE, bool KN = false, bool HU = false>
 __global__ void __launch_bounds__(256)
 k_margin_pad(const crthip_params P, int n_fields, signed char *__restrict__ dst, size_t fstride, int shift,
              const crthip_state *__restrict__ state, const uint2 *__restrict__ jump16, const uint2 *__restrict__ jump1,
@@ -1166,7 +1228,8 @@ k_margin_pad(const crthip_params P, int n_fields, signed char *__restrict__ dst,
     const int var = skeleton_variant<S>(st->field, st->frame, st->aux);
     signed char *out = dst + (size_t) f * fstride + shift;
     const v4i sk = load16u(skel + (size_t) var * skel_stride + idx0);
-    const int wds[4] = { sk.x, sk.y, sk.z, sk.w };
+    typename std::conditional<HU, int, const int>::type wds[4] = { sk.x, sk.y, sk.z, sk.w };
+    if constexpr (HU) hue_patch_burst<S>(P, hue_blob_recs(P) + f, st, line, col, wds);
     v4i pk;
     if (NOISE) {
         unsigned rn;
@@ -1190,7 +1253,7 @@ k_margin_pad(const crthip_params P, int n_fields, signed char *__restrict__ dst,
         pk.z = (int) pack4(vals[8], vals[9], vals[10], vals[11]);
         pk.w = (int) pack4(vals[12], vals[13], vals[14], vals[15]);
     } else {
-        pk = sk;
+        pk.x = wds[0]; pk.y = wds[1]; pk.z = wds[2]; pk.w = wds[3];
     }
     signed char *home = out + line * G::PITCH + col;
     if (len == 16) {
@@ -1229,7 +1292,9 @@ static bool encoder_fast_ok(const crthip_ctx *c, const crthip_params *p)
      * let white up to 2^23 into the fast kernels, where the product could wrap differently from the reference's; nothing sane is near.) */
     bool ok = wh < (1 << 13) && ib < (1 << 13) && nz < (1 << 15);
     if (p->flags & CRTHIP_F_HIPASS) ok = false;                   /* the debug build's high-pass lives in the exact kernels */
-    for (int r = 0; r < CRTHIP_CARRIER_ROWS; r++)                  /* ... and so are the carriers * 4096 */
+    /* (a call with hue records, crthip_bind_hues: crthip_knobs_prepare8 has checked every field's carriers against this very bound
+     * and refuses a batch with one outside it; the blob's own tables are not the call's) */
+    for (int r = 0; r < CRTHIP_CARRIER_ROWS && !hue_call(c); r++)  /* ... and so are the carriers * 4096 */
         for (int k = 0; k < CRTHIP_MAX_CCS; k++)
             ok = ok && p->modI[r][k] > -2048 && p->modI[r][k] < 2048 && p->modQ[r][k] > -2048 && p->modQ[r][k] < 2048;
     if (S::BANDLIMIT)                                              /* the forms of the 64-bit low-passes (k_active) */
@@ -1272,11 +1337,23 @@ static void launch_active(crthip_ctx *c, const crthip_params *p, int n, const vo
     constexpr bool LVS = FULL && !S::IS_NES && S::CCS == 4;
     const bool lv = LVS && level_call(c);
     (void) lv;
+    /* per-field encoder hue: the HU instantiations, of the same shapes, with the level records (lv) or with the blob's white and
+     * ire_base (a hue-only binding) */
+    const bool hu = LVS && hue_call(c);
+    (void) hu;
     if constexpr (!S::IS_NES) {
         /* kernel shape (crthip_set_shape): small batches take the scanline-parallel encoder */
         if (c->shape == 2 || (c->shape == 0 && n <= ROWS_SHAPE_MAX_FIELDS_ENC)) {
             const dim3 rgrid((total + 7) / 8);
             if constexpr (LVS) {
+#define CRTHIP_LAUNCH_ACTIVE_ROW_HU(NZ, KNV, LVV) \
+    hipLaunchKernelGGL((k_active_row<S, NZ, true, KNV, LVV, true>), rgrid, block, 0, c->stream, *p, n, img, istride, dst, lay.fstride, d_state, c->d_jump16, c->d_jump1, lay.pitch, lay.shift, wrapn)
+                if (hu) {
+                    if (lv) { if (kn) CRTHIP_LAUNCH_ACTIVE_ROW_HU(true, true, true); else CRTHIP_LAUNCH_ACTIVE_ROW_HU(false, false, true); }
+                    else    { if (kn) CRTHIP_LAUNCH_ACTIVE_ROW_HU(true, true, false); else CRTHIP_LAUNCH_ACTIVE_ROW_HU(false, false, false); }
+                    return;
+                }
+#undef CRTHIP_LAUNCH_ACTIVE_ROW_HU
                 if (lv) {
                     if (kn) hipLaunchKernelGGL((k_active_row<S, true, true, true, true>), rgrid, block, 0, c->stream, *p, n, img, istride, dst, lay.fstride, d_state, c->d_jump16, c->d_jump1, lay.pitch, lay.shift, wrapn);
                     else hipLaunchKernelGGL((k_active_row<S, false, true, false, true>), rgrid, block, 0, c->stream, *p, n, img, istride, dst, lay.fstride, d_state, c->d_jump16, c->d_jump1, lay.pitch, lay.shift, wrapn);
@@ -1324,7 +1401,11 @@ static void launch_active(crthip_ctx *c, const crthip_params *p, int n, const vo
 #define CRTHIP_LAUNCH_ACTIVE_BIG(NZ, ...) \
     do { if (wide_in) hipLaunchKernelGGL((k_active<S, NZ, true, true, true, 32, 64, CRTHIP_ENC_OL64 __VA_ARGS__>), ogrid, block, 0, c->stream, *p, n, img, istride, dst, lay.fstride, d_state, c->d_jump16, bo.K, bo.per, lay.pitch, lay.shift, wrapn); \
          else hipLaunchKernelGGL((k_active<S, NZ, true, true, true, 16, 32, CRTHIP_ENC_OL32 __VA_ARGS__>), ogrid, block, 0, c->stream, *p, n, img, istride, dst, lay.fstride, d_state, c->d_jump16, bo.K, bo.per, lay.pitch, lay.shift, wrapn); } while (0)
-            if (lv) { if (kn) CRTHIP_LAUNCH_ACTIVE_BIG(true, , true, true); else CRTHIP_LAUNCH_ACTIVE_BIG(false, , false, true); }
+            if (hu) {
+                if (lv) { if (kn) CRTHIP_LAUNCH_ACTIVE_BIG(true, , true, true, true); else CRTHIP_LAUNCH_ACTIVE_BIG(false, , false, true, true); }
+                else    { if (kn) CRTHIP_LAUNCH_ACTIVE_BIG(true, , true, false, true); else CRTHIP_LAUNCH_ACTIVE_BIG(false, , false, false, true); }
+            }
+            else if (lv) { if (kn) CRTHIP_LAUNCH_ACTIVE_BIG(true, , true, true); else CRTHIP_LAUNCH_ACTIVE_BIG(false, , false, true); }
             else if (kn) CRTHIP_LAUNCH_ACTIVE_BIG(true, , true);
             else if (noise) CRTHIP_LAUNCH_ACTIVE_BIG(true); else CRTHIP_LAUNCH_ACTIVE_BIG(false);
 #undef CRTHIP_LAUNCH_ACTIVE_BIG
@@ -1335,6 +1416,14 @@ static void launch_active(crthip_ctx *c, const crthip_params *p, int n, const vo
     do { if (wide_in) hipLaunchKernelGGL((k_active<S, NZ, FAST, I4, FULL, 32 __VA_ARGS__>), ogrid, block, 0, c->stream, *p, n, img, istride, dst, lay.fstride, d_state, c->d_jump16, bo.K, bo.per, lay.pitch, lay.shift, wrapn); \
          else hipLaunchKernelGGL((k_active<S, NZ, FAST, I4, FULL, 16 __VA_ARGS__>), ogrid, block, 0, c->stream, *p, n, img, istride, dst, lay.fstride, d_state, c->d_jump16, bo.K, bo.per, lay.pitch, lay.shift, wrapn); } while (0)
     if constexpr (LVS) {
+        if (hu) {                                                /* (the default tiles spelt out: KN, LV and HU are the last parameters) */
+#define CRTHIP_LAUNCH_ACTIVE_HU(NZ, KNV, LVV) \
+    do { if (in4) CRTHIP_LAUNCH_ACTIVE(NZ, true, , 16, 16, KNV, LVV, true); else CRTHIP_LAUNCH_ACTIVE(NZ, false, , 16, 16, KNV, LVV, true); } while (0)
+            if (lv) { if (kn) CRTHIP_LAUNCH_ACTIVE_HU(true, true, true); else CRTHIP_LAUNCH_ACTIVE_HU(false, false, true); }
+            else    { if (kn) CRTHIP_LAUNCH_ACTIVE_HU(true, true, false); else CRTHIP_LAUNCH_ACTIVE_HU(false, false, false); }
+#undef CRTHIP_LAUNCH_ACTIVE_HU
+            return;
+        }
         if (lv) {                                                /* (the default tiles spelt out: KN and LV are the last parameters) */
             if (kn) { if (in4) CRTHIP_LAUNCH_ACTIVE(true, true, , 16, 16, true, true); else CRTHIP_LAUNCH_ACTIVE(true, false, , 16, 16, true, true); }
             else    { if (in4) CRTHIP_LAUNCH_ACTIVE(false, true, , 16, 16, false, true); else CRTHIP_LAUNCH_ACTIVE(false, false, , 16, 16, false, true); }
@@ -1365,6 +1454,17 @@ static void launch_margins(crthip_ctx *c, const crthip_params *p, int n, signed 
     const int per_field = head + (p->desth - 1) * gap + tail;
     const unsigned gap_magic = gap > 0 ? (unsigned) ((0x100000000ull + (unsigned) gap - 1) / (unsigned) gap) : 0u;
     const dim3 grid((per_field + 255) / 256, n < 65535 ? n : 65535);          /* (fields beyond the grid's y limit: the kernel loops) */
+    if constexpr (!S::IS_NES && S::CCS == 4) {
+        if (hue_call(c)) {                                       /* (a knob call: its noise is per field, or the batch's largest is 0) */
+            if (p->noise != 0)
+                hipLaunchKernelGGL((k_margin<S, true, true, true>), grid, dim3(256), 0, c->stream,
+                                   *p, n, dst, c->fstride, d_state, c->d_jump16, c->d_jump1, c->d_skel, head, gap, tail, gap_magic);
+            else
+                hipLaunchKernelGGL((k_margin<S, false, false, true>), grid, dim3(256), 0, c->stream,
+                                   *p, n, dst, c->fstride, d_state, c->d_jump16, c->d_jump1, c->d_skel, head, gap, tail, gap_magic);
+            return;
+        }
+    }
     if (p->noise != 0 && c->knob_recs)
         hipLaunchKernelGGL((k_margin<S, true, true>), grid, dim3(256), 0, c->stream,
                            *p, n, dst, c->fstride, d_state, c->d_jump16, c->d_jump1, c->d_skel, head, gap, tail, gap_magic);
@@ -1390,6 +1490,17 @@ static void launch_margins_padded(crthip_ctx *c, const crthip_params *p, int n, 
     const unsigned act_magic = act_per > 1 ? (unsigned) ((0x100000000ull + (unsigned) act_per - 1) / (unsigned) act_per) : 0u;
     const int per_field = p->yo * CF + p->desth * act_per + (S::VRES - p->yo - p->desth) * CF;
     const dim3 grid((per_field + 255) / 256, n < 65535 ? n : 65535);
+    if constexpr (!S::IS_NES && S::CCS == 4) {
+        if (hue_call(c)) {
+            if (p->noise != 0)
+                hipLaunchKernelGGL((k_margin_pad<S, true, true, true>), grid, dim3(256), 0, c->stream, *p, n, dst, lay.fstride, lay.shift, d_state,
+                                   c->d_jump16, c->d_jump1, c->d_skel, c->fstride, cl, cr, act_magic, lay.wrap);
+            else
+                hipLaunchKernelGGL((k_margin_pad<S, false, false, true>), grid, dim3(256), 0, c->stream, *p, n, dst, lay.fstride, lay.shift, d_state,
+                                   c->d_jump16, c->d_jump1, c->d_skel, c->fstride, cl, cr, act_magic, lay.wrap);
+            return;
+        }
+    }
     if (p->noise != 0 && c->knob_recs)
         hipLaunchKernelGGL((k_margin_pad<S, true, true>), grid, dim3(256), 0, c->stream, *p, n, dst, lay.fstride, lay.shift, d_state,
                            c->d_jump16, c->d_jump1, c->d_skel, c->fstride, cl, cr, act_magic, lay.wrap);
@@ -1447,19 +1558,22 @@ static int launch_encoder(crthip_ctx *c, const crthip_params *p, int n, const vo
 
 /* after crt_modulate: ccf preset (crt_ntsc.c:325-329, crt_nes.c:196-200, crt_snes.c:238-240,321-325),
  * VHS resets (crt_ntscvhs.c:259,332-336) */
-template <class S>
+/* HU: the burst table of the field's own crthip_hue_rec */
+template <class S, bool HU = false>
 __global__ void k_encoder_state(const crthip_params P, int n_fields, crthip_state *state)
 {
     const int f = blockIdx.x * blockDim.x + threadIdx.x;
     if (f >= n_fields) return;
     crthip_state *st = state + f;
+    const crthip_hue_rec *hr = nullptr;
+    if constexpr (HU) hr = hue_blob_recs(P) + f;
     if constexpr (S::LINE_ROWS) {
         /* iccf[(n + CCF_SHIFT) % VPER][t % CCS] is last written by the bottom-most line of its class; all lines of
          * a class write the same burst, so any line n of the class will do */
         for (int cls = 0; cls < S::VPER; cls++) {
             const int row = carrier_row<S>(cls, st->field, st->frame, st->aux);
             for (int k = 0; k < S::CCS; k++) {
-                const int cb = P.burst[row][k];
+                const int cb = HU ? hr->burst[row][k] : P.burst[row][k];
                 st->ccf[(cls + S::CCF_SHIFT) % S::VPER][k] = ((int) (signed char) ((S::BLANK + cb * S::BURST) >> 5)) << 7;
             }
         }
@@ -1470,7 +1584,7 @@ __global__ void k_encoder_state(const crthip_params P, int n_fields, crthip_stat
     } else {
         const int row = carrier_row<S>(0, st->field, st->frame, st->aux);
         for (int k = 0; k < 4; k++) {
-            const int cb = P.burst[row][k];
+            const int cb = HU ? hr->burst[row][k] : P.burst[row][k];
             const int v = ((int) (signed char) ((S::BLANK + cb * S::BURST) >> 5)) << 7;
             st->ccf[0][k] = S::IS_VHS ? 0 : v;
         }
@@ -1478,6 +1592,18 @@ __global__ void k_encoder_state(const crthip_params P, int n_fields, crthip_stat
         st->field &= 1;
         st->frame &= 1;
     }
+}
+
+template <class S>
+static void launch_encoder_state(crthip_ctx *c, const crthip_params *p, int n, crthip_state *d_state)
+{
+    if constexpr (!S::IS_NES && S::CCS == 4) {
+        if (hue_call(c)) {
+            hipLaunchKernelGGL((k_encoder_state<S, true>), dim3((n + 63) / 64), dim3(64), 0, c->stream, *p, n, d_state);
+            return;
+        }
+    }
+    hipLaunchKernelGGL((k_encoder_state<S>), dim3((n + 63) / 64), dim3(64), 0, c->stream, *p, n, d_state);
 }
 
 /* Encoder tables that depend on the parameter blob only (clean skeleton variants, NES sample table): (re)built on
@@ -1516,7 +1642,18 @@ int crt_run_encoder_prepare(crthip_ctx *c, const crthip_params *p, bool fused)
         const int border_key[4] = { p->flags & CRTHIP_F_NES_BORDER, p->nes_border_color, p->black_point, p->white_point };
         const bool border_same = !(p->flags & CRTHIP_F_NES_BORDER) ? c->skel_border[0] == 0
                                                                     : memcmp(c->skel_border, border_key, sizeof(border_key)) == 0;
-        const bool need_skel = fused && (!c->skel_valid || memcmp(c->skel_burst, p->burst, sizeof(p->burst)) != 0 || c->skel_yo != p->yo || !border_same);
+        /* a call with hue records (crthip_bind_hues): the margin kernels recompute every burst byte from the records, so whatever
+         * burst the cached variants were built from serves -- such a call never rebuilds them for their burst; where there are none
+         * yet, they are built from the caller's own table (two words of which the blob lends to the records' pointer, crt_dev.h) */
+        crthip_params own;
+        if (hue_call(c)) {
+            own = *p;
+            own.burst[0][0] = c->hue_burst0[0];
+            own.burst[0][1] = c->hue_burst0[1];
+            p = &own;
+        }
+        const bool burst_same = hue_call(c) || memcmp(c->skel_burst, p->burst, sizeof(p->burst)) == 0;
+        const bool need_skel = fused && (!c->skel_valid || !burst_same || c->skel_yo != p->yo || !border_same);
         bool need_nes = false;
         if constexpr (S::IS_NES) need_nes = !c->nes_tab_valid || c->nes_tab_black != p->black_point || c->nes_tab_white != p->white_point;
 
@@ -1600,7 +1737,7 @@ int crt_run_encoder(crthip_ctx *c, const crthip_params *p, int n, const void *d_
         const sig_layout &ly = lay && fused ? *lay : flat;
         int r = fused ? launch_encoder<S, true>(c, p, n, d_images, istride, dst, d_state, nes_setup, ly)
                       : launch_encoder<S, false>(c, p, n, d_images, istride, dst, d_state, nes_setup, ly);
-        if (with_state) hipLaunchKernelGGL((k_encoder_state<S>), dim3((n + 63) / 64), dim3(64), 0, c->stream, *p, n, d_state);
+        if (with_state) launch_encoder_state<S>(c, p, n, d_state);
         return r;
     });
 }
@@ -1610,7 +1747,7 @@ int crt_run_encoder_state(crthip_ctx *c, const crthip_params *p, int n, crthip_s
 {
     return dispatch_system(c->system, c->pattern, [&](auto tag) {
         using S = decltype(tag);
-        hipLaunchKernelGGL((k_encoder_state<S>), dim3((n + 63) / 64), dim3(64), 0, c->stream, *p, n, d_state);
+        launch_encoder_state<S>(c, p, n, d_state);
         return CRTHIP_OK;
     });
 }

@@ -981,6 +981,7 @@ static int fieldpass_chunk(crthip_ctx *c, const crthip_params *p, int enc, int f
         pk = *p;
         knob_blob_set(&pk, c->knob_recs + first);
         if (level_call(c)) level_blob_set(&pk, level_blob_get(p) + first);
+        if (hue_call(c)) hue_blob_set(&pk, hue_blob_get(p) + first);
         p = &pk;
     }
     if (part & 1) {
@@ -1014,6 +1015,7 @@ static int fieldpass_chunk(crthip_ctx *c, const crthip_params *p, int enc, int f
                  * leaves in the state (ccf preset, M6) is applied by the sync chain's own waves when it follows at once
                  * (k_hsync_wave, preset_ccf): one launch less per field-pass */
                 preset = (part & 4) && p->out_bpp != 0 && c->system != CRTHIP_SYSTEM_NTSCVHS;   /* (VHS also resets hsync there) */
+                if (hue_call(c)) preset = false;      /* the preset comes from every field's own burst table: k_encoder_state's HU instantiation */
                 rc = crt_run_encoder(c, p, n, img, istride, inp, st, true, 1, !preset, &lay);
             } else {
                 /* invalid input format: crt_modulate is a no-op, the decoder sees a clean field + noise
@@ -1140,6 +1142,7 @@ static bool knobs_env_pic_ok(const crthip_knobs_env *env)
 static int knobs_blob(crthip_ctx *c, const crthip_params *p, int n, const crthip_knob_rec *d_recs, const crthip_knobs_env *env, crthip_params *q)
 {
     c->lev_on = 0;
+    c->hue_on = 0;
     if (!d_recs || !env) return CRTHIP_E_ARG;
     if (CHECK_WORD(c, d_recs)) return CRTHIP_E_ARG;
     if (env->magic != CRTHIP_KNOBS_MAGIC) return set_err(c, CRTHIP_E_ARG, "knobs: env does not come from crthip_knobs_prepare", hipSuccess);
@@ -1160,6 +1163,12 @@ static int knobs_blob(crthip_ctx *c, const crthip_params *p, int n, const crthip
         if (c->system == CRTHIP_SYSTEM_NES)
             return set_err(c, CRTHIP_E_ARG, "levels: the NES encoder's samples come from a 512 x 12 table built for ONE (black point, white point) pair", hipSuccess);
     }
+    /* hue records bound (crthip_bind_hues): likewise, and independently of the levels */
+    if (c->hue_recs) {
+        if (c->hue_env.n != n) return set_err(c, CRTHIP_E_ARG, "hues: the bound crthip_hues_env was prepared for another number of fields", hipSuccess);
+        if (c->system == CRTHIP_SYSTEM_NES)
+            return set_err(c, CRTHIP_E_ARG, "hues: the NES encoder (PPU pixels) has no per-field instantiation", hipSuccess);
+    }
     c->knob_pic = env->pic;
     c->knob_floor_lo = env->pic ? (env->tier_floors & 0xff) : 0;
     *q = *p;
@@ -1171,6 +1180,14 @@ static int knobs_blob(crthip_ctx *c, const crthip_params *p, int n, const crthip
          * the launch code decides by c->lev_env where it read them (encoder_fast_ok) */
         level_blob_set(q, c->lev_recs);
         c->lev_on = 1;
+    }
+    if (c->hue_recs) {
+        /* the HU kernels read burst / modI / modQ from the records; two words of the blob's burst table carry the pointer to them
+         * (crt_dev.h), the caller's own two are kept for the skeleton cache (crt_run_encoder_prepare) */
+        c->hue_burst0[0] = p->burst[0][0];
+        c->hue_burst0[1] = p->burst[0][1];
+        hue_blob_set(q, c->hue_recs);
+        c->hue_on = 1;
     }
     c->knob_loskip = env->loskip_wave_max < LOSKIP_WAVE_MAX ? LOSKIP_WAVE_MAX : env->loskip_wave_max > T0_WAVE_MAX ? T0_WAVE_MAX : env->loskip_wave_max;
     return CRTHIP_OK;
@@ -1696,6 +1713,20 @@ int crthip_bind_levels(crthip_ctx *c, const crthip_level_rec *d_levs, const crth
     if (lenv->n <= 0 || lenv->white_abs_max < 0 || lenv->ire_base_abs_max < 0) return set_err(c, CRTHIP_E_ARG, "levels: lenv bounds", hipSuccess);
     c->lev_recs = d_levs;
     c->lev_env = *lenv;
+    return CRTHIP_OK;
+}
+
+/* The encoder's hue records for the knob entry points (crt_hip.h, HUE KNOB): as crthip_bind_levels. */
+int crthip_bind_hues(crthip_ctx *c, const crthip_hue_rec *d_hues, const crthip_hues_env *henv)
+{
+    if (!c) return CRTHIP_E_ARG;
+    if (!d_hues && !henv) { c->hue_recs = nullptr; return CRTHIP_OK; }
+    if (!d_hues || !henv) return set_err(c, CRTHIP_E_ARG, "crthip_bind_hues: records and env go together ((NULL, NULL) unbinds)", hipSuccess);
+    if (check_word(c, d_hues, "d_hues needs 4-byte alignment")) return CRTHIP_E_ARG;
+    if (henv->magic != CRTHIP_HUES_MAGIC) return set_err(c, CRTHIP_E_ARG, "hues: henv does not come from crthip_knobs_prepare8", hipSuccess);
+    if (henv->n <= 0) return set_err(c, CRTHIP_E_ARG, "hues: henv bounds", hipSuccess);
+    c->hue_recs = d_hues;
+    c->hue_env = *henv;
     return CRTHIP_OK;
 }
 

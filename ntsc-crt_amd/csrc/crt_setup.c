@@ -375,6 +375,49 @@ crthip_phosphor_table(int age, unsigned char lut[256])
     return CRTHIP_OK;
 }
 
+/* The three carrier tables of the RGB-input encoders for one encoder hue (the tables zeroed by the caller): what
+ * crthip_params_finalize keeps in crthip_params, and crthip_knobs_prepare8 in every field's crthip_hue_rec. */
+static void
+rgb_carriers(const struct crt_sysdef *d, int chroma_pattern, int as_color, int hue,
+             int burst[CRTHIP_CARRIER_ROWS][CRTHIP_MAX_CCS], int modI[CRTHIP_CARRIER_ROWS][CRTHIP_MAX_CCS],
+             int modQ[CRTHIP_CARRIER_ROWS][CRTHIP_MAX_CCS])
+{
+    const int step = 360 / d->cc_samples;
+    int k, r, sn, cs, rows;
+
+    if (as_color || d->nes_timing) {                            /* NES-RGB has no as_color member: always colour */
+        rows = d->line_rows ? CRTHIP_CARRIER_ROWS : 1;
+        for (r = 0; r < rows; r++) {
+            for (k = 0; k < d->cc_samples; k++) {
+                /* crt_ntsc.c:175-182; crt_snes.c:171-182; crt_pv1k.c:167-178; crt_nesrgb.c:67-78 */
+                int ang = r * d->vert_step + k * step;
+                int hue_mod = d->hue_in_mod ? hue : 0;
+                crt_setup_sincos14(&sn, &cs, (ang + hue + d->burst_off) * 8192 / 180);
+                burst[r][k] = sn >> 10;
+                crt_setup_sincos14(&sn, &cs, (ang + hue_mod) * 8192 / 180);
+                modI[r][k] = sn >> 10;
+                crt_setup_sincos14(&sn, &cs, (ang + hue_mod + d->q_off) * 8192 / 180);
+                modQ[r][k] = sn >> 10;
+            }
+        }
+        if (!d->line_rows) {
+            /* row 1 = the lines of a field whose parity equals the frame's (inv_phase, crt_ntsc.c:199-200,
+             * 243-247): burst advanced by half a cycle, modulation carriers negated -- CRT_CHROMA_PATTERN 1 only */
+            for (k = 0; k < 4; k++) {
+                if (chroma_pattern == 1) {
+                    burst[1][k] = burst[0][(k + 2) & 3];
+                    modI[1][k] = -modI[0][k];
+                    modQ[1][k] = -modQ[0][k];
+                } else {
+                    burst[1][k] = burst[0][k];
+                    modI[1][k] = modI[0][k];
+                    modQ[1][k] = modQ[0][k];
+                }
+            }
+        }
+    }
+}
+
 int
 crthip_params_finalize(crthip_params *p)
 {
@@ -387,7 +430,7 @@ crthip_params_finalize(crthip_params *p)
         { 65536, 12192, 7775 }, { 65536, 65536, 1311 }, { 65536, 65536, 0 }
     };
     struct crt_sysdef d;
-    int k, r, sn, cs, rows;
+    int k, r, sn, cs;
 
     if (p == 0 || crt_sysdef_get(&d, p->system, p->chroma_pattern) != CRTHIP_OK) {
         return CRTHIP_E_ARG;
@@ -443,7 +486,6 @@ crthip_params_finalize(crthip_params *p)
             }
         }
     } else {
-        const int step = 360 / d.cc_samples;
         p->in_bpp = crt_setup_bpp4fmt(p->format);
         /* geometry: crt_ntsc.c:132-133, 148-173, 194-203; crt_nesrgb.c:51-52, 85-89 */
         p->destw = d.av_len;
@@ -470,37 +512,7 @@ crthip_params_finalize(crthip_params *p)
         } else {
             p->xo &= ~3;
         }
-        if (p->as_color || d.nes_timing) {                      /* NES-RGB has no as_color member: always colour */
-            rows = d.line_rows ? CRTHIP_CARRIER_ROWS : 1;
-            for (r = 0; r < rows; r++) {
-                for (k = 0; k < d.cc_samples; k++) {
-                    /* crt_ntsc.c:175-182; crt_snes.c:171-182; crt_pv1k.c:167-178; crt_nesrgb.c:67-78 */
-                    int ang = r * d.vert_step + k * step;
-                    int hue_mod = d.hue_in_mod ? p->hue : 0;
-                    crt_setup_sincos14(&sn, &cs, (ang + p->hue + d.burst_off) * 8192 / 180);
-                    p->burst[r][k] = sn >> 10;
-                    crt_setup_sincos14(&sn, &cs, (ang + hue_mod) * 8192 / 180);
-                    p->modI[r][k] = sn >> 10;
-                    crt_setup_sincos14(&sn, &cs, (ang + hue_mod + d.q_off) * 8192 / 180);
-                    p->modQ[r][k] = sn >> 10;
-                }
-            }
-            if (!d.line_rows) {
-                /* row 1 = the lines of a field whose parity equals the frame's (inv_phase, crt_ntsc.c:199-200,
-                 * 243-247): burst advanced by half a cycle, modulation carriers negated -- CRT_CHROMA_PATTERN 1 only */
-                for (k = 0; k < 4; k++) {
-                    if (p->chroma_pattern == 1) {
-                        p->burst[1][k] = p->burst[0][(k + 2) & 3];
-                        p->modI[1][k] = -p->modI[0][k];
-                        p->modQ[1][k] = -p->modQ[0][k];
-                    } else {
-                        p->burst[1][k] = p->burst[0][k];
-                        p->modI[1][k] = p->modI[0][k];
-                        p->modQ[1][k] = p->modQ[0][k];
-                    }
-                }
-            }
-        }
+        rgb_carriers(&d, p->chroma_pattern, p->as_color, p->hue, p->burst, p->modI, p->modQ);
         if (d.y_freq != 0) {
             int yf = d.y_freq, jf = d.i_freq, qf = d.q_freq;
             if (p->system == CRTHIP_SYSTEM_NTSCVHS && (p->flags & CRTHIP_F_VHS_LP)) {        /* crt_ntscvhs.h:114-118 */
@@ -830,6 +842,48 @@ crthip_knobs_prepare7(const crthip_params *p, int n, const crthip_knobs7 *knobs,
         return CRTHIP_E_ARG;
     }
     return knobs_prepare_any(p, n, knobs ? &knobs->noise : 0, (int) (sizeof(*knobs) / sizeof(int)), 1, recs, env, levs, lenv);
+}
+
+/* The same with the encoder hue per field: the first seven values exactly as crthip_knobs_prepare7 takes them (the signal range the
+ * env's no-low-cascade bound comes from does not move with the hue: |burst| <= 32, so the burst samples stay inside sync level ..
+ * white level), and hues[k] = the carrier tables crthip_params_finalize derives for field k's hue (crthip_bind_hues).  What that
+ * function would refuse for a field is refused here: the PPU encoder, which has no per-field instantiation, and -- checked, although
+ * sn >> 10 cannot give it -- a carrier outside the 24-bit encoder's bound (encoder_fast_ok, crt_encode.hip). */
+int
+crthip_knobs_prepare8(const crthip_params *p, int n, const crthip_knobs8 *knobs, crthip_knob_rec *recs, crthip_level_rec *levs,
+                      crthip_hue_rec *hues, crthip_knobs_env *env, crthip_levels_env *lenv, crthip_hues_env *henv)
+{
+    struct crt_sysdef d;
+    int k, r, i, rc;
+
+    if (levs == 0 || lenv == 0 || hues == 0 || henv == 0) {
+        return CRTHIP_E_ARG;
+    }
+    rc = knobs_prepare_any(p, n, knobs ? &knobs->noise : 0, (int) (sizeof(*knobs) / sizeof(int)), 1, recs, env, levs, lenv);
+    if (rc != CRTHIP_OK) {
+        return rc;
+    }
+    if (crt_sysdef_get(&d, p->system, p->chroma_pattern) != CRTHIP_OK || d.ppu_input) {
+        return CRTHIP_E_ARG;
+    }
+    for (k = 0; k < n; k++) {
+        if (knobs[k].hue > CRTHIP_HUE_ABS_MAX || knobs[k].hue < -CRTHIP_HUE_ABS_MAX) {
+            return CRTHIP_E_ARG;                                    /* (angle * 8192 must stay an int) */
+        }
+        memset(&hues[k], 0, sizeof(hues[k]));
+        rgb_carriers(&d, p->chroma_pattern, p->as_color, knobs[k].hue, hues[k].burst, hues[k].modI, hues[k].modQ);
+        for (r = 0; r < CRTHIP_CARRIER_ROWS; r++) {
+            for (i = 0; i < CRTHIP_MAX_CCS; i++) {
+                if (hues[k].modI[r][i] <= -2048 || hues[k].modI[r][i] >= 2048 || hues[k].modQ[r][i] <= -2048 || hues[k].modQ[r][i] >= 2048) {
+                    return CRTHIP_E_ARG;
+                }
+            }
+        }
+    }
+    memset(henv, 0, sizeof(*henv));
+    henv->magic = CRTHIP_HUES_MAGIC;
+    henv->n = n;
+    return CRTHIP_OK;
 }
 
 /*
