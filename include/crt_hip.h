@@ -260,7 +260,9 @@ int  crthip_reserve(crthip_ctx *ctx, int n_fields);
  *              ONLY; with CRTHIP_F_IMAGE_SPARE_ROW one more row (w*bpp bytes) behind each image is read as well, without it not a
  *              byte.  image_stride >= those bytes, otherwise free (the images need not be packed).  Base AND stride: multiples of
  *              4 for the 4-byte pixel formats (the kernels load whole pixels as dwords), of 2 for PPU pixels, any for RGB / BGR.
- *   d_out, out_stride      : picture k = the outw*outh*bpp bytes from d_out + k*out_stride, read (blend, rows the field does not
+ *              crthip_stills_knobs alone also takes image_stride == 0: every still then reads the ONE image at d_images (and its one
+ *              spare row with CRTHIP_F_IMAGE_SPARE_ROW).
+ *   d_out, out_stride     : picture k = the outw*outh*bpp bytes from d_out + k*out_stride, read (blend, rows the field does not
  *              own, the phosphor flags) and written; out_stride >= those bytes, otherwise free.  Base and stride: multiples of 4
  *              for the 4-byte formats (pixels are stored as dwords and 16-byte runs of dwords), any for RGB / BGR.
  *   d_out_init, out_init_stride : as d_out / out_stride, READ ONLY (out_init_stride 0 = one shared picture).
@@ -392,8 +394,8 @@ int  crthip_fieldpass(crthip_ctx *ctx, const crthip_params *p, int n,
  * REFUSED (CRTHIP_E_ARG, crthip_error_string says why, nothing launched, d_out and d_state untouched): a henv whose magic or n does
  * not match; d_hues off its 4-byte alignment; CRTHIP_SYSTEM_PV1K (as for every knob); CRTHIP_SYSTEM_NES, whose PPU encoder has no
  * per-field instantiation (as for the levels).
- * OUT OF SCOPE: as_color and raw per field (keys SPACE and t), NES and PV-1000, knobs in crthip_stills, knob videos through
- * shard.py / crt_hip_node.h.
+ * OUT OF SCOPE: as_color and raw per field (keys SPACE and t), NES and PV-1000, knob videos through shard.py / crt_hip_node.h.
+ * (Finished stills with one look per still: crthip_stills_knobs, under STILLS below.)
  */
 typedef struct crthip_knobs     { int noise, mon_hue, saturation, reserved; } crthip_knobs;                                /* 16 bytes */
 typedef struct crthip_knobs5    { int noise, mon_hue, saturation, brightness, contrast, reserved[3]; } crthip_knobs5;      /* 32 bytes */
@@ -548,6 +550,30 @@ int  crthip_sequence_sets_knobs(crthip_ctx *ctx, const crthip_params *p,
  *   - the shared signal lives in a workspace of its own: nothing of it is seen by a following crthip_fieldpass / crthip_sequence*
  *     on the same context, nor the other way round.  crthip_fieldpass_signal after crthip_stills is refused (the passes of a still
  *     may have read different signals; there is no "the" signal of the call).
+ *
+ * crthip_stills_knobs: finished stills, EACH WITH ITS OWN LOOK -- an augmentation set, a parameter sweep, a contact sheet of one image
+ * under n looks.  Bit for bit and state for state what n_passes calls of crthip_fieldpass_knobs give on the same n images, d_out,
+ * d_state and records, d_state[k].field / .frame / .aux set to sched[r] before call r exactly as above; record k is still k's look
+ * in EVERY pass.  Per still k that is the reference's loop on one struct CRT whose hue, saturation, brightness, contrast,
+ * black_point and white_point are still k's, with NTSC_SETTINGS.hue still k's and crt_demodulate(noise_k) in every pass.
+ *   d_recs / env : exactly as for crthip_fieldpass_knobs -- the records of crthip_knobs_prepare / 5 / 7 / 8 over the n stills, uploaded
+ *   by the caller; level records (crthip_bind_levels) and hue records (crthip_bind_hues) are read while bound and require lenv->n == n
+ *   / henv->n == n.  Nothing of the call survives it; crthip_stills itself behaves as before whether or not something is bound.
+ *   Accepted: everything crthip_stills accepts, with the same meaning per pass (every 4-sample system, bloom with max_e per still,
+ *   FIR, both kernel shapes and signal layouts, CRTHIP_F_NES_SETUP, the phosphor flags, the rand()-noise VHS build with bound
+ *   histories: one generator per still).  Refused (CRTHIP_E_ARG, crthip_error_string says why, nothing launched, d_out and d_state
+ *   untouched): what crthip_stills refuses and what crthip_fieldpass_knobs refuses -- CRTHIP_SYSTEM_PV1K, an env whose magic or n
+ *   does not match or whose picture words contradict each other, both phosphor flags at once, d_recs off its alignment, and with
+ *   levels or hues bound the NES (with levels also CRTHIP_F_NES_BORDER).
+ *   The shared clean signal: env->noise_max == 0 (every still at noise 0) under the other conditions of crthip_stills' shared path
+ *   -- every distinct (field, frame, aux) is encoded once for the batch, with the records' blob: the LV / HU encoder instantiations
+ *   when levels / hues are bound (still k's clean signal depends on ITS levels and hue, not on the pass), into the same workspace
+ *   (crthip_stills_reserve).  rn, the ccf preset (from the hue record when hues are bound) and the VHS hsync reset are applied per
+ *   pass.  A batch in which ANY still has noise above 0 encodes per pass, as the loop does.
+ *   Asynchronous and capturable like crthip_stills after crthip_stills_reserve; records rewritten between replays must stay inside
+ *   the captured env / lenv / henv (the rule of crthip_fieldpass_knobs).  crthip_fieldpass_signal after the call is refused.
+ *   image_stride == 0 is accepted HERE: every still reads the one image at d_images -- exactly the call with n identical images,
+ *   without the n copies (with CRTHIP_F_IMAGE_SPARE_ROW the one spare row behind that image is read).
  */
 typedef struct crthip_pass { int field, frame, aux, reserved; } crthip_pass;     /* 16 bytes */
 #define CRTHIP_STILLS_MAX_PASSES 64
@@ -558,6 +584,11 @@ int  crthip_stills(crthip_ctx *ctx, const crthip_params *p, int n,
                    const void *d_images, size_t image_stride,
                    void *d_out, size_t out_stride, crthip_state *d_state,
                    int n_passes, const crthip_pass *sched /* host */);
+int  crthip_stills_knobs(crthip_ctx *ctx, const crthip_params *p, int n,
+                         const void *d_images, size_t image_stride,
+                         void *d_out, size_t out_stride, crthip_state *d_state,
+                         int n_passes, const crthip_pass *sched /* host */,
+                         const crthip_knob_rec *d_recs /* n, DEVICE */, const crthip_knobs_env *env /* host */);
 
 /*
  * The phases of crthip_sequence, for hosts that cut ONE video over several contexts / devices / processes

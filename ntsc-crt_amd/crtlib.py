@@ -274,6 +274,8 @@ def load_library():
         L.crthip_knobs_prepare8.argtypes = [PP, ci, C.POINTER(Knobs8), C.POINTER(KnobRec), C.POINTER(LevelRec), C.POINTER(HueRec),
                                             C.POINTER(KnobsEnv), C.POINTER(LevelsEnv), C.POINTER(HuesEnv)]
         L.crthip_bind_hues.argtypes = [vp, vp, C.POINTER(HuesEnv)]
+    if hasattr(L, "crthip_stills_knobs"):                         # (likewise)
+        L.crthip_stills_knobs.argtypes = [vp, PP, ci, vp, sz, vp, sz, vp, ci, C.POINTER(Pass), vp, C.POINTER(KnobsEnv)]
     _LIB = L
     return L
 
@@ -564,8 +566,8 @@ class CRT:
         d = s.data
         row = d.stride(1) * d.element_size()
         need = (int(d.shape[1]) + 1) * row
-        if d.shape[0] > 1 and d.stride(0) * d.element_size() < need:
-            return False
+        if d.shape[0] > 1 and d.stride(0) != 0 and d.stride(0) * d.element_size() < need:
+            return False                                           # (stride(0) == 0: ONE image expanded to n, stills_knobs)
         last = (d.storage_offset() + (int(d.shape[0]) - 1) * d.stride(0)) * d.element_size() + need
         return d.untyped_storage().nbytes() >= last
 
@@ -701,17 +703,41 @@ class CRT:
         zeros, rn 194.  ``schedule``: a list of (field, frame) or (field, frame, aux) per pass instead of the CLI's, e.g. dot-crawl
         offsets r % CRT_CC_VPER in aux for NES / PV-1000, aberration heights for VHS.  At noise 0 every distinct entry is encoded
         once.  ``s.field`` / ``s.frame`` / ``s.dot_crawl_offset`` / ``s.aberration`` are not used: the schedule gives them."""
+        buf = self._stills_passes(interlaced, first_field, frames, schedule)
+        p = self.params(s, noise)
+        rc = self.L.crthip_stills(self.ctx, C.byref(p), self.n, C.c_void_p(s.data.data_ptr()), self._image_stride(s),
+                                  C.c_void_p(self.out.data_ptr()), self.out.stride(0), C.c_void_p(self.state.data_ptr()),
+                                  len(buf), buf)
+        self._check(rc, "crthip_stills")
+        s.initialized = 1
+
+    @staticmethod
+    def _stills_passes(interlaced, first_field, frames, schedule):
+        """the crthip_pass array of stills() / stills_knobs(): the CLI's schedule, or the caller's list"""
         sched = stills_schedule(interlaced, first_field, frames) if schedule is None else [tuple(e) for e in schedule]
         if not 0 < len(sched) <= STILLS_MAX_PASSES:
             raise ValueError("a stills schedule has 1 .. %d passes, not %d" % (STILLS_MAX_PASSES, len(sched)))
         buf = (Pass * len(sched))()
         for r, e in enumerate(sched):
             buf[r].field, buf[r].frame, buf[r].aux = int(e[0]), int(e[1]), int(e[2]) if len(e) > 2 else 0
-        p = self.params(s, noise)
-        rc = self.L.crthip_stills(self.ctx, C.byref(p), self.n, C.c_void_p(s.data.data_ptr()), self._image_stride(s),
-                                  C.c_void_p(self.out.data_ptr()), self.out.stride(0), C.c_void_p(self.state.data_ptr()),
-                                  len(sched), buf)
-        self._check(rc, "crthip_stills")
+        return buf
+
+    def stills_knobs(self, s, knobs, interlaced=True, first_field=0, frames=4, schedule=None, params=None):
+        """stills with one look per still: ``knobs`` = an (n, 3), (n, 5), (n, 7) or (n, 8) integer array or tensor as for
+        fieldpass_knobs, row k = still k's look in every pass (None: the records and bounds of the last upload_knobs -- inside a
+        graph capture).  The schedule is that of stills().  With every still at noise 0 each distinct entry is encoded once, with
+        every still's own levels and hue.  ``s.data`` may be ONE image expanded to n (``img[None].expand(n, ...)``, stride(0) == 0):
+        the contact sheet of an image under n looks, without n copies of it."""
+        buf = self._stills_passes(interlaced, first_field, frames, schedule)
+        p = params if params is not None else self.params(s, 0)
+        if knobs is not None:
+            self.upload_knobs(knobs, p)
+        if self.knob_recs is None:
+            raise ValueError("stills_knobs(s, None): no knobs uploaded yet (upload_knobs)")
+        rc = self.L.crthip_stills_knobs(self.ctx, C.byref(p), self.n, C.c_void_p(s.data.data_ptr()), self._image_stride(s),
+                                        C.c_void_p(self.out.data_ptr()), self.out.stride(0), C.c_void_p(self.state.data_ptr()),
+                                        len(buf), buf, C.c_void_p(self.knob_recs.data_ptr()), C.byref(self._knob_env))
+        self._check(rc, "crthip_stills_knobs")
         s.initialized = 1
 
     def sequence(self, s, noise, out_init=None):

@@ -1249,8 +1249,10 @@ int crthip_stills_reserve(crthip_ctx *c, int n, int n_distinct)
     return stills_workspace(c, (size_t) n * n_distinct, 0);
 }
 
-int crthip_stills(crthip_ctx *c, const crthip_params *p, int n, const void *d_images, size_t istride,
-                  void *d_out, size_t ostride, crthip_state *d_state, int n_passes, const crthip_pass *sched)
+/* crthip_stills, and crthip_stills_knobs when c->knob_recs is set (p is then the library's copy carrying the batch's bounds: p->noise
+ * = the call's largest noise, which decides the shared path) */
+static int stills_body(crthip_ctx *c, const crthip_params *p, int n, const void *d_images, size_t istride,
+                       void *d_out, size_t ostride, crthip_state *d_state, int n_passes, const crthip_pass *sched)
 {
     int rc = check_params(c, p, n);
     if (rc) return rc;
@@ -1319,8 +1321,10 @@ int crthip_stills(crthip_ctx *c, const crthip_params *p, int n, const void *d_im
     }
     /* what crt_modulate leaves in the state is applied per pass: by the sync chain's own waves (preset_ccf), or -- VHS, which also
      * resets hsync there -- by k_encoder_state, exactly as a field-pass does */
-    const bool preset = c->system != CRTHIP_SYSTEM_NTSCVHS;
-    const crthip_params q = with_signal_envelope(p);
+    /* (hue records: the preset comes from every still's own burst table, k_encoder_state's HU instantiation, as in a field-pass) */
+    const bool preset = c->system != CRTHIP_SYSTEM_NTSCVHS && !hue_call(c);
+    crthip_params q = c->knob_recs ? *p : with_signal_envelope(p);
+    if (c->knob_recs) q.loskip_wave_max = c->knob_loskip;     /* the envelope at the batch's widest noise (crthip_knobs_prepare) */
     unsigned char *out = (unsigned char *) d_out;
     for (int r = 0; r < n_passes; r++) {
         const signed char *sig = c->d_still_sig + (size_t) slot[r] * slot_bytes;
@@ -1337,6 +1341,31 @@ int crthip_stills(crthip_ctx *c, const crthip_params *p, int n, const void *d_im
     }
     HIPCHK(c, hipGetLastError());
     return CRTHIP_OK;
+}
+
+int crthip_stills(crthip_ctx *c, const crthip_params *p, int n, const void *d_images, size_t istride,
+                  void *d_out, size_t ostride, crthip_state *d_state, int n_passes, const crthip_pass *sched)
+{
+    if (c) c->knob_recs = nullptr;
+    return stills_body(c, p, n, d_images, istride, d_out, ostride, d_state, n_passes, sched);
+}
+
+/* record k is still k's look in every pass: every launch of the body reads the records the way a field-pass of the n stills does.
+ * With the call's largest noise 0 the clean signal of every distinct entry is encoded once WITH the blob of the records (the LV / HU
+ * instantiations where levels / hues are bound: a still's clean signal depends on its own levels and hue, not on the pass). */
+int crthip_stills_knobs(crthip_ctx *c, const crthip_params *p, int n, const void *d_images, size_t istride,
+                        void *d_out, size_t ostride, crthip_state *d_state, int n_passes, const crthip_pass *sched,
+                        const crthip_knob_rec *d_recs, const crthip_knobs_env *env)
+{
+    int rc = check_params(c, p, n);
+    if (rc) return rc;
+    crthip_params q;
+    rc = knobs_blob(c, p, n, d_recs, env, &q);
+    if (rc) return rc;
+    c->knob_recs = d_recs;
+    rc = stills_body(c, &q, n, d_images, istride, d_out, ostride, d_state, n_passes, sched);
+    c->knob_recs = nullptr;
+    return rc;
 }
 
 unsigned crthip_table_generation(const crthip_ctx *c) { return c ? c->table_gen : 0u; }
