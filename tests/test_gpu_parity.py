@@ -1,11 +1,18 @@
 """GPU parity tests proper: the HIP path (through the crthip_* C ABI) against the CPU oracle on
 the same seeded inputs.  Bit-exact: this is integer/byte work, tolerance = 0.  Every stage the
 reference exposes through struct CRT is compared (analog, inp, ccf, hsync, vsync, rn, out) plus
-the internal per-line sync chain."""
+the internal per-line sync chain.
+
+The inputs live in tests/parity_cases.py.  tests/test_parity_pin_cpu.py proves on the CPU that the oracle equals the real reference
+(oracle/_ref) on every one of them, and wherever that build travelled with the tree (crtref.have_ref) _run_case, the NES table, the
+VHS tests and the wild sync states hold the GPU to the reference's own bytes as well: the oracle's comparison comes first, because
+it localises a failure to a stage and a line."""
 import numpy as np
 import pytest
 
 import crtref as R
+import parity_cases as P
+from parity_cases import CASES, F4_CASES, NES_CASES, WIDE_CASES
 
 pytestmark = pytest.mark.gpu
 
@@ -47,50 +54,27 @@ def _oracle_batch(name, n, outw, outh, ofmt, knobs):
     return orc, crts
 
 
-CASES = [
-    # name, outw, outh, ofmt, w, h, ifmt, noise, settings, knobs
-    ("ntsc", 640, 480, R.FMT_BGRA, 640, 480, R.FMT_BGRA, 0, dict(as_color=1), {}),
-    ("ntsc", 640, 480, R.FMT_BGRA, 640, 480, R.FMT_BGRA, 24, dict(as_color=1), dict(scanlines=1)),
-    ("ntsc", 832, 624, R.FMT_ARGB, 640, 480, R.FMT_ABGR, 40, dict(as_color=1, hue=350), dict(hue=17, saturation=14)),
-    ("ntsc", 640, 480, R.FMT_RGB, 320, 200, R.FMT_RGB, 12, dict(as_color=1, hue=30), dict(blend=1)),
-    ("ntsc", 1920, 1080, R.FMT_RGBA, 1920, 1080, R.FMT_BGR, 0, dict(as_color=1), dict(scanlines=1)),
-    ("ntsc", 1920, 1080, R.FMT_BGRA, 1920, 1080, R.FMT_BGRA, 0, dict(as_color=1), dict(scanlines=0, blend=1)),
-    ("ntsc", 753, 240, R.FMT_ABGR, 753, 236, R.FMT_RGBA, 5, dict(as_color=0), dict(brightness=9, contrast=200)),
-    ("ntsc", 500, 300, R.FMT_BGR, 200, 100, R.FMT_ARGB, 60, dict(as_color=1, raw=1), dict(black_point=3, white_point=90)),
-    ("ntsc", 333, 481, R.FMT_RGB, 100, 300, R.FMT_RGB, 100, dict(as_color=1, raw=1, xoffset=8, yoffset=2), dict(v_fac=10)),
-    ("ntsc", 257, 243, R.FMT_BGRA, 800, 600, R.FMT_BGRA, 24, dict(as_color=1, hue=180), dict(scanlines=1, blend=1)),
-    # between the envelopes: saturation 40 puts the carrier above tier 0's bound (lines flagged NOT64, tier 1),
-    # brightness 5000 lifts the whole batch to tier 1
-    ("ntsc", 640, 480, R.FMT_BGRA, 640, 480, R.FMT_BGRA, 24, dict(as_color=1), dict(saturation=40)),
-    ("ntsc", 640, 480, R.FMT_BGRA, 640, 480, R.FMT_BGRA, 24, dict(as_color=1), dict(brightness=5000, contrast=20)),
-    ("ntsc", 640, 480, R.FMT_BGRA, 640, 480, R.FMT_BGRA, 60, dict(as_color=1), dict(brightness=-2600, saturation=24)),
-    # either side of tier 0's chroma bound (|wave| <= 65532: I/Q low cascades dropped), with heavy noise
-    ("ntsc", 640, 480, R.FMT_BGRA, 640, 480, R.FMT_BGRA, 110, dict(as_color=1, hue=77), dict(saturation=13)),
-    ("ntsc", 640, 480, R.FMT_BGRA, 640, 480, R.FMT_BGRA, 110, dict(as_color=1, hue=77), dict(saturation=14)),
-    # outside the 24-bit multiply envelope: huge saturation (lines flagged CRTHIP_LINE_EXACT by k_sync) ...
-    ("ntsc", 640, 480, R.FMT_BGRA, 640, 480, R.FMT_BGRA, 30, dict(as_color=1), dict(saturation=900, contrast=300)),
-    # ... and huge brightness / contrast / white point (host-side check picks the exact kernels)
-    ("ntsc", 640, 480, R.FMT_RGBA, 640, 480, R.FMT_RGBA, 10, dict(as_color=1), dict(brightness=200000, contrast=9000000, white_point=9000000)),
-    ("ntsc", 320, 240, R.FMT_BGRA, 320, 240, R.FMT_BGRA, 50000000, dict(as_color=1), dict(saturation=-70)),
-    # standard NTSC built with CRT_CHROMA_PATTERN 0 (HRES 912, vertical chroma, no phase flip)
-    ("ntscp0", 640, 480, R.FMT_BGRA, 640, 480, R.FMT_BGRA, 24, dict(as_color=1, hue=40), dict(scanlines=1)),
-    ("ntscp0", 832, 624, R.FMT_RGB, 320, 240, R.FMT_BGR, 0, dict(as_color=1, raw=1), dict(blend=1)),
-    # outh < CRT_LINES: several CRT lines land on one output row; sequential semantics incl. blend chains
-    ("ntsc", 640, 200, R.FMT_BGRA, 640, 480, R.FMT_BGRA, 24, dict(as_color=1), dict(blend=1)),
-    ("ntsc", 101, 77, R.FMT_RGB, 64, 48, R.FMT_RGB, 10, dict(as_color=1), dict(scanlines=1)),
-    ("ntsc", 64, 120, R.FMT_ABGR, 64, 48, R.FMT_BGRA, 0, dict(as_color=1), dict(blend=1, v_fac=30)),
-]
+def _checkers(name):
+    """the oracle, and the real reference beside it wherever its build of `name` is there (oracle/_ref travels with the tree): the
+    oracle localises a failure to a stage and a line, the reference's bytes are what the GPU is held to"""
+    libs = [("oracle", R.Oracle(name))]
+    if R.have_ref(name):
+        libs.append(("reference", R.RefLib(name)))
+    return libs
 
 
-def _run_case(crtlib, case, fused, steps=4, n=3, exact=False, shape=1, sig_tile=0, wide_lpw=0, sig_pad=1, want_padded=None):
+def _run_case(crtlib, case, fused, steps=4, n=3, exact=False, shape=1, sig_tile=0, wide_lpw=0, sig_pad=1, want_padded=None, table=None):
     """shape: 1 = lane-per-scanline kernels (the throughput shape; forced, because small batches would otherwise
     pick the other one), 2 = scanline-parallel kernels, 0 = the library's own choice;  wide_lpw: 8 / 16 pins the wide-run
-    decoder's scanlines per wavefront (0: by batch size, i.e. 8 for the small batches of these tests)"""
+    decoder's scanlines per wavefront (0: by batch size, i.e. 8 for the small batches of these tests);  table: the table of
+    tests/parity_cases.py the case belongs to -- its recorded exclusions say whether a field may drop out of the comparison.
+    The inputs, the field walk and the checkers' set-up are parity_cases'; tests/test_parity_pin_cpu.py runs the same ones."""
     name, outw, outh, ofmt, w, h, ifmt, noise, skw, knobs = case
-    bpp = R.bpp4fmt(ifmt)
-    imgs = np.stack([R.synth_image(w, h, bpp, 777 + 13 * k, "random" if k % 2 == 0 else "bars") for k in range(n)])
+    imgs = P.images(case, n)
     dimgs = _padded(imgs)
-    orc, ocrts = _oracle_batch(name, n, outw, outh, ofmt, knobs)
+    libs = _checkers(name)
+    orc = libs[0][1]
+    crts = [[P.checker_crt(lib, case, k, imgs[k]) for k in range(n)] for _, lib in libs]
     g = crtlib.CRT(n, outw, outh, ofmt, name[:4] if name.startswith("ntscfir") else name, device=0)
     g.eq_fir = R.EQ_KERNEL.get(name, 0)              # "ntscfir7": the FIR decoder of a USE_CONVOLUTION build
     g.set_exact(exact)
@@ -100,19 +84,13 @@ def _run_case(crtlib, case, fused, steps=4, n=3, exact=False, shape=1, sig_tile=
     g.set_signal_layout(sig_pad)                     # fused path: padded signal lines (round 6) or the reference's flat ones
     for k, v in knobs.items():
         setattr(g, k, v)
-    fields = [k & 1 for k in range(n)]
-    frames = [(k >> 1) & 1 for k in range(n)]
     dot_crawl = orc.system in R.DOT_CRAWL_SYSTEMS      # SNES, template, PV-1000: NTSC_SETTINGS.dot_crawl_offset
-    dcos = [(2 * k + 1) % 6 if name.startswith(("pv1k", "temp")) else (k + 1) % 3 for k in range(n)]
-    s = crtlib.Settings(dimgs, format=ifmt, field=list(fields), frame=list(frames),
-                        dot_crawl_offset=list(dcos) if dot_crawl else 0, **skw)
-    for k, c in enumerate(ocrts):
-        pad = np.concatenate([imgs[k], imgs[k][-1:]], axis=0)
-        c.settings(pad, format=ifmt, w=w, h=h, field=fields[k], frame=frames[k], **skw)
-        if dot_crawl:
-            c.sset("dot_crawl_offset", dcos[k])
+    s = crtlib.Settings(dimgs, format=ifmt, field=[P.field_of(k, 0) for k in range(n)], frame=[P.frame_of(k, 0) for k in range(n)],
+                        dot_crawl_offset=[P.dco_of(name, k) for k in range(n)] if dot_crawl else 0, **skw)
     undefined = [False] * n
     for step in range(steps):
+        # the interlaced sequence (video_convert.c:259-267)
+        s.field, s.frame = [P.field_of(k, step) for k in range(n)], [P.frame_of(k, step) for k in range(n)]
         if fused:
             g.fieldpass(s, noise)
         else:
@@ -136,52 +114,53 @@ def _run_case(crtlib, case, fused, steps=4, n=3, exact=False, shape=1, sig_tile=
                 assert was_padded == want_padded, "signal layout of the fused path: padded=%s" % was_padded
         else:
             fsig = None
-        for k, c in enumerate(ocrts):
-            what = "%s fused=%s step %d field %d" % (name, fused, step, k)
-            c.modulate()
-            if not fused and not undefined[k]:
-                np.testing.assert_array_equal(analog[k, :orc.input_size], c.analog, err_msg=what + " analog")
-                np.testing.assert_array_equal(ccf_mod[k, :orc.vper, :orc.ccs], c.ccf, err_msg=what + " ccf after modulate")
-            hs_before = c.get("hsync")
-            c.demodulate(noise, trace=True)
-            # a sync state far from lock on the field's last analog line makes the REFERENCE read past inp[] + 16 (heavy noise):
-            # undefined there, different bytes here -- the field is out of the comparison from then on
-            undefined[k] = undefined[k] or R.reads_past_inp(orc, c.trace, c.get("vsync"), hs_before)
-            if undefined[k]:
-                continue
-            if fused and fsig is not None:
-                np.testing.assert_array_equal(fsig[k, :orc.input_size], c.inp, err_msg=what + " inp of the fused path")
-            if not fused:
-                np.testing.assert_array_equal(ginp[k, :orc.input_size], c.inp, err_msg=what + " inp")
-                tr = c.trace
-                valid = tr[:, 0] == 1
-                np.testing.assert_array_equal((glines[k][:, 4] & 0xffff) > 0, valid, err_msg=what + " valid lines")
-                np.testing.assert_array_equal(glines[k][valid][:, [0, 1, 2, 3, 5, 6, 7]], tr[valid][:, [1, 2, 3, 4, 6, 7, 8]],
-                                              err_msg=what + " line table (pos, wave0, wave1, beg, hsync, dx, scanl)")
-            for f in ("hsync", "vsync", "rn"):
-                assert gst[f][k] == c.get(f), "%s %s: gpu %d oracle %d" % (what, f, gst[f][k], c.get(f))
-            np.testing.assert_array_equal(gccf[k, :orc.vper, :orc.ccs], c.ccf, err_msg=what + " ccf")
-            np.testing.assert_array_equal(gout[k].reshape(-1), c.out, err_msg=what + " out")
-        # next field: interlaced sequence (video_convert.c:259-267)
-        fields = [f ^ 1 for f in fields]
-        if step % 2 == 0:
-            frames = [f ^ 1 for f in frames]
-        s.field, s.frame = list(fields), list(frames)
-        for k, c in enumerate(ocrts):
-            c.sset("field", fields[k])
-            c.sset("frame", frames[k])
+        for k in range(n):
+            for (tag, lib), per in zip(libs, crts):
+                c = per[k]
+                what = "%s fused=%s step %d field %d, against the %s:" % (name, fused, step, k, tag)
+                P.checker_walk(lib, c, k, step)
+                c.modulate()
+                if not fused and not undefined[k]:
+                    np.testing.assert_array_equal(analog[k, :orc.input_size], c.analog, err_msg=what + " analog")
+                    np.testing.assert_array_equal(ccf_mod[k, :orc.vper, :orc.ccs], c.ccf, err_msg=what + " ccf after modulate")
+                if lib is not orc:
+                    c.demodulate(noise)
+                else:
+                    hs_before = c.get("hsync")
+                    c.demodulate(noise, trace=True)
+                    # a sync state far from lock on the field's last analog line makes the REFERENCE read past inp[] + 16 (heavy noise):
+                    # undefined there, different bytes here -- the field is out of the comparison from then on
+                    undefined[k] = undefined[k] or R.reads_past_inp(orc, c.trace, c.get("vsync"), hs_before)
+                if undefined[k]:
+                    continue
+                if fused and fsig is not None:
+                    np.testing.assert_array_equal(fsig[k, :orc.input_size], c.inp, err_msg=what + " inp of the fused path")
+                if not fused:
+                    np.testing.assert_array_equal(ginp[k, :orc.input_size], c.inp, err_msg=what + " inp")
+                if not fused and lib is orc:
+                    tr = c.trace
+                    valid = tr[:, 0] == 1
+                    np.testing.assert_array_equal((glines[k][:, 4] & 0xffff) > 0, valid, err_msg=what + " valid lines")
+                    np.testing.assert_array_equal(glines[k][valid][:, [0, 1, 2, 3, 5, 6, 7]], tr[valid][:, [1, 2, 3, 4, 6, 7, 8]],
+                                                  err_msg=what + " line table (pos, wave0, wave1, beg, hsync, dx, scanl)")
+                for f in ("hsync", "vsync", "rn"):
+                    assert gst[f][k] == c.get(f), "%s %s: gpu %d, %d there" % (what, f, gst[f][k], c.get(f))
+                np.testing.assert_array_equal(gccf[k, :orc.vper, :orc.ccs], c.ccf, err_msg=what + " ccf")
+                np.testing.assert_array_equal(gout[k].reshape(-1), c.out, err_msg=what + " out")
     g.close()
     assert not all(undefined), "every field fell into the reference's undefined behaviour: the case checks nothing"
+    if table is not None and P.excludes_nothing(table):
+        assert not any(undefined), "a field of table %s fell into the reference's undefined behaviour: parity_cases.EXCLUDED records none" % table
 
 
 @pytest.mark.parametrize("case", range(len(CASES)))
 def test_stagewise_parity(crtlib, case):
-    _run_case(crtlib, CASES[case], fused=False)
+    _run_case(crtlib, CASES[case], fused=False, table="CASES")
 
 
 @pytest.mark.parametrize("case", range(len(CASES)))
 def test_fused_fieldpass_parity(crtlib, case):
-    _run_case(crtlib, CASES[case], fused=True)
+    _run_case(crtlib, CASES[case], fused=True, table="CASES")
 
 
 @pytest.mark.parametrize("case", range(len(CASES)))
@@ -189,20 +168,18 @@ def test_fused_fieldpass_flat_signal_layout_parity(crtlib, case):
     """Round 6: the fused path keeps its signal in PADDED lines by default (crt_dev.h, sig_layout; every other fused test runs that).
     The reference's flat layout is still what geometries outside the padded layout's reach, sequence mode and every stage-level
     call use: forced here (crthip_set_signal_layout(ctx, 0)) for the whole table, inp[] compared as well."""
-    _run_case(crtlib, CASES[case], fused=True, steps=2, sig_pad=0, want_padded=False)
+    _run_case(crtlib, CASES[case], fused=True, steps=2, sig_pad=0, want_padded=False, table="CASES")
 
 
 @pytest.mark.parametrize("sig_tile", [0, 32])
-@pytest.mark.parametrize("name,case", [("ntsc", 0), ("ntsc", 1), ("ntsc", 2), ("ntsc", 5), ("ntsc", 9), ("ntsc", 13), ("ntscp0", 18), ("snes", 1), ("temp", 1),
-                                       ("pv1k", 1), ("nesrgb", 1), ("ntscbloom", 1), ("pv1kbloom", 1), ("vhslcg", 1), ("ntscnovsync", 1)])
+@pytest.mark.parametrize("name,case", P.PADDED_LAYOUT)
 def test_padded_signal_layout_is_what_the_fused_path_runs(crtlib, name, case, sig_tile):
     """... and the default really is the padded layout for every system at its standard geometry (crthip_fieldpass_signal reports
     which layout the workspace held), with inp[] -- repacked to the reference's layout -- equal to the oracle's byte for byte, all
     shapes of the sync chain's windows included (four steps: the sync state moves).  The rand()-noise VHS build and CRT_DO_VSYNC 0
     produce their signal by other kernels and stay flat; so does the VHS build with the LCG noise (one system is one layout)."""
-    c = CASES[case] if name.startswith("ntsc") and not name.endswith(("bloom", "novsync")) or name == "ntscp0" else (name,) + F4_CASES[case]
-    c = (name,) + tuple(c[1:])
-    _run_case(crtlib, c, fused=True, steps=4, sig_tile=sig_tile, want_padded=name not in ("vhslcg", "ntscnovsync"))
+    _run_case(crtlib, P.padded_layout_case(name, case), fused=True, steps=4, sig_tile=sig_tile, want_padded=name not in ("vhslcg", "ntscnovsync"),
+              table="CASES" if name in ("ntsc", "ntscp0") else "PADDED_LAYOUT")
 
 
 def test_padded_signal_layout_falls_back_for_rows_it_cannot_hold(crtlib):
@@ -210,42 +187,26 @@ def test_padded_signal_layout_falls_back_for_rows_it_cannot_hold(crtlib):
     crt_ntsc.c:322: the row continues in the next line's front porch) and outside the padded layout: the flat one takes it.  Up to
     16 samples (xoffset 4: 3 samples, xoffset 16: 15) the padded layout stores the overhang twice -- behind its line and at the
     head of the next (RowTiles::wrap_home)."""
-    for xoff, padded in ((24, False), (16, True), (4, True)):
-        case = ("ntsc", 640, 480, R.FMT_BGRA, 640, 480, R.FMT_BGRA, 30, dict(as_color=1, xoffset=xoff, yoffset=1), dict(scanlines=1))
-        _run_case(crtlib, case, fused=True, steps=2, want_padded=padded)
-        _run_case(crtlib, case, fused=True, steps=2, want_padded=padded, shape=2)      # the scanline-parallel encoder's stores
+    for xoff, padded in P.LAYOUT_FALLBACK_XOFFSETS:
+        case = P.layout_fallback_case(xoff)
+        _run_case(crtlib, case, fused=True, steps=2, want_padded=padded, table="LAYOUT_FALLBACK")
+        _run_case(crtlib, case, fused=True, steps=2, want_padded=padded, shape=2, table="LAYOUT_FALLBACK")      # the scanline-parallel encoder's stores
 
 
 @pytest.mark.parametrize("fused", [False, True])
-@pytest.mark.parametrize("taps", [7, 6, 5, 4])
-@pytest.mark.parametrize("case", [1, 2, 4, 8])
+@pytest.mark.parametrize("taps", P.FIR_TAPS)
+@pytest.mark.parametrize("case", P.FIR_CASES)
 def test_fir_decoder_parity(crtlib, case, taps, fused):
     """the decoder of a USE_CONVOLUTION build of the reference (crt_core.c:85-147, symmetric FIR
     kernels of 7/6/5/4 taps instead of the 3-band equaliser), selected per launch with CRTHIP_F_EQ_FIR(taps).
     The oracle's FIR mode is pinned against those builds of the reference in tests/test_oracle_vs_ref.py."""
-    c = CASES[case]
-    _run_case(crtlib, ("ntscfir%d" % taps,) + tuple(c[1:]), fused=fused, steps=2)
+    _run_case(crtlib, P.renamed("ntscfir%d" % taps, CASES[case]), fused=fused, steps=2, table="FIR")
 
 
-@pytest.mark.parametrize("knobs", [dict(saturation=900, contrast=300), dict(brightness=200000, contrast=9000000, white_point=9000000)])
+@pytest.mark.parametrize("knobs", P.FIR_ENVELOPE_KNOBS)
 def test_fir_decoder_outside_the_24bit_envelope(crtlib, knobs):
     """huge carrier amplitude (lines flagged by k_hsync) / huge brightness (host-side floor): the exact FIR tier"""
-    _run_case(crtlib, ("ntscfir7", 640, 480, R.FMT_BGRA, 640, 480, R.FMT_BGRA, 30, dict(as_color=1), knobs), fused=True, steps=2)
-
-
-WIDE_CASES = [
-    # name, outw, outh, ofmt, w, h, ifmt, noise, settings, knobs -- pictures the 16-scanlines-per-wave decoder takes (crt_decode4.hip)
-    ("ntsc", 1920, 1080, R.FMT_BGRA, 1920, 1080, R.FMT_BGRA, 0, dict(as_color=1), dict(scanlines=1)),
-    ("ntsc", 1920, 1080, R.FMT_ARGB, 640, 480, R.FMT_RGB, 24, dict(as_color=1, hue=40), dict(scanlines=0, hue=-20, saturation=14)),
-    ("ntsc", 2047, 777, R.FMT_ABGR, 333, 100, R.FMT_ABGR, 60, dict(as_color=0), dict(scanlines=1, v_fac=100, brightness=12, contrast=250)),
-    ("ntsc", 1700, 300, R.FMT_RGBA, 1281, 601, R.FMT_BGRA, 12, dict(as_color=1, raw=1), dict(scanlines=1, black_point=-5, white_point=120)),
-    ("snes", 1920, 1080, R.FMT_BGRA, 640, 480, R.FMT_BGRA, 24, dict(as_color=1), dict(scanlines=1)),
-    ("temp", 1664, 1248, R.FMT_BGRA, 832, 624, R.FMT_BGRA, 0, dict(as_color=1), dict(scanlines=1)),
-    ("ntscp0", 1920, 1200, R.FMT_BGRA, 1920, 1080, R.FMT_RGBA, 24, dict(as_color=1), dict(scanlines=1)),
-    # strong carriers: some 64-scanline groups leave tiers 0 / 1 and stay with the lane-per-scanline kernel, their neighbours do not
-    ("ntsc", 1920, 1080, R.FMT_BGRA, 640, 480, R.FMT_BGRA, 24, dict(as_color=1), dict(scanlines=1, saturation=25)),
-    ("ntsc", 1920, 1080, R.FMT_BGRA, 640, 480, R.FMT_BGRA, 40, dict(as_color=1), dict(scanlines=1, saturation=60, contrast=300)),
-]
+    _run_case(crtlib, P.fir_envelope_case(knobs), fused=True, steps=2, table="FIR_ENVELOPE")
 
 
 @pytest.mark.parametrize("lpw", [8, 16])
@@ -254,7 +215,7 @@ def test_wide_decoder_parity(crtlib, case, lpw):
     """crt_decode4.hip (round 4): 16 scanlines per wave, a scanline's four filter cascades on four lanes, pixels lane-per-pixel in
     1 KB row runs -- fused, three steps, every field against the oracle (out, state, ccf).  Both instantiations pinned
     (crthip_set_wide_lpw): k_decode_wide<S, 16> is what the 1080p bench batches run, <S, 8> what small batches pick by themselves."""
-    _run_case(crtlib, WIDE_CASES[case], fused=True, steps=3, n=5, wide_lpw=lpw)
+    _run_case(crtlib, WIDE_CASES[case], fused=True, steps=3, n=5, wide_lpw=lpw, table="WIDE_CASES")
 
 
 @pytest.mark.parametrize("lpw", [8, 16])
@@ -262,9 +223,9 @@ def test_wide_decoder_parity(crtlib, case, lpw):
 def test_wide_decoder_stagewise_and_tiers(crtlib, case, lpw):
     """... stage by stage (line table compared too), and with the decoder tiers forced: tier 1 runs in the wide kernel,
     tiers 2 / 3 hand the whole batch back to the lane-per-scanline kernel"""
-    _run_case(crtlib, WIDE_CASES[case], fused=False, steps=2, n=3, wide_lpw=lpw)
+    _run_case(crtlib, WIDE_CASES[case], fused=False, steps=2, n=3, wide_lpw=lpw, table="WIDE_CASES")
     for mode in (1, 2, 3):
-        _run_case(crtlib, WIDE_CASES[case], fused=True, exact=mode, steps=1, n=2, wide_lpw=lpw)
+        _run_case(crtlib, WIDE_CASES[case], fused=True, exact=mode, steps=1, n=2, wide_lpw=lpw, table="WIDE_CASES")
 
 
 def test_wide_decoder_against_the_lane_per_scanline_decoder(crtlib):
@@ -322,7 +283,7 @@ def test_large_signal_tiles_parity(crtlib, case):
     """the fused encoder with its LARGE signal tile (128-byte pieces beside the narrow image tile, 256-byte pieces beside the wide
     one: what batches of thousands of fields take, crt_encode.hip launch_active) forced onto every case of the table, against the
     oracle; the library's own choice at these batch sizes is the 64-byte tile of every other test"""
-    _run_case(crtlib, CASES[case], fused=True, steps=2, sig_tile=64)
+    _run_case(crtlib, CASES[case], fused=True, steps=2, sig_tile=64, table="CASES")
 
 
 @pytest.mark.parametrize("mode", [1, 2, 3])
@@ -331,7 +292,7 @@ def test_slower_decoder_tiers_parity(crtlib, case, mode):
     """ordinary inputs normally run decoder tier 0 (64-bit mads, no I/Q low cascades); force tier 3 (mode 1:
     exact 32-bit multiplies everywhere), tier 2 (mode 2: 24-bit mads) and tier 1 (mode 3: 64-bit mads, all
     cascades) onto them"""
-    _run_case(crtlib, CASES[case], fused=True, exact=mode, steps=2)
+    _run_case(crtlib, CASES[case], fused=True, exact=mode, steps=2, table="CASES")
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -341,23 +302,22 @@ def test_slower_decoder_tiers_parity(crtlib, case, mode):
 @pytest.mark.parametrize("case", range(len(CASES)))
 def test_scanline_parallel_shape_parity(crtlib, case, fused):
     """every case of the table, decoded by the scanline-parallel kernels instead of the lane-per-scanline ones"""
-    _run_case(crtlib, CASES[case], fused=fused, shape=2, steps=2)
+    _run_case(crtlib, CASES[case], fused=fused, shape=2, steps=2, table="CASES")
 
 
 @pytest.mark.parametrize("mode", [1, 3])
 @pytest.mark.parametrize("case", [1, 2, 5])
 def test_scanline_parallel_wide_variant_on_ordinary_inputs(crtlib, case, mode):
     """ordinary inputs take the 16-lane (NARROW) variant; set_exact 1 / 3 force the 32-lane one with all 6 cascades"""
-    _run_case(crtlib, CASES[case], fused=True, exact=mode, shape=2, steps=2)
+    _run_case(crtlib, CASES[case], fused=True, exact=mode, shape=2, steps=2, table="CASES")
 
 
 def test_library_picks_the_shape_by_batch_size(crtlib):
     """crthip_set_shape(0): small batches -> scanline-parallel, large ones -> lane-per-scanline; same pictures.  The signal layout
     follows the encoder (round 6, crt_fused_layout): flat lines with the scanline-parallel encoder the library picks for up to 256
     fields, padded lines with the lane-per-row one."""
-    _run_case(crtlib, CASES[1], fused=True, shape=0, steps=2, n=2, want_padded=False)
-    _run_case(crtlib, ("ntsc", 96, 240, R.FMT_BGRA, 64, 48, R.FMT_BGRA, 24, dict(as_color=1), dict(scanlines=1)),
-              fused=True, shape=0, steps=1, n=300, want_padded=True)
+    _run_case(crtlib, CASES[1], fused=True, shape=0, steps=2, n=2, want_padded=False, table="CASES")
+    _run_case(crtlib, P.SHAPE_PICK_CASE, fused=True, shape=0, steps=1, n=P.SHAPE_PICK_N, want_padded=True, table="SHAPE_PICK")
 
 
 def test_the_nes_keeps_flat_signal_lines(crtlib):
@@ -384,97 +344,79 @@ def test_the_nes_keeps_flat_signal_lines(crtlib):
         np.testing.assert_array_equal(sig[k, :orc.input_size].cpu().numpy(), c.inp, err_msg="NES field %d: inp of the fused path" % k)
         np.testing.assert_array_equal(g.out[k].cpu().numpy().reshape(-1), c.out)
     g.close()
-    _run_case(crtlib, ("nesrgb",) + F4_CASES[1], fused=True, steps=2, want_padded=True)
+    _run_case(crtlib, P.padded_layout_case("nesrgb", 1), fused=True, steps=2, want_padded=True, table="PADDED_LAYOUT")
 
 
 # ---------------------------------------------------------------------------------------------------------------
 # SNES, template, PV-1000 (5 samples per chroma cycle), NES-RGB;  8(f3): CRT_DO_BLOOM builds
 # ---------------------------------------------------------------------------------------------------------------
-F4_CASES = [
-    # outw, outh, ofmt, w, h, ifmt, noise, settings, knobs
-    (640, 480, R.FMT_BGRA, 640, 480, R.FMT_BGRA, 0, dict(as_color=1), {}),
-    (640, 480, R.FMT_BGRA, 640, 480, R.FMT_BGRA, 24, dict(as_color=1, hue=25), dict(scanlines=1)),
-    (832, 624, R.FMT_ARGB, 640, 480, R.FMT_ABGR, 40, dict(as_color=1, hue=350), dict(hue=17, saturation=14)),
-    (640, 480, R.FMT_RGB, 320, 200, R.FMT_RGB, 12, dict(as_color=1, hue=-57), dict(blend=1)),
-    (500, 300, R.FMT_BGR, 200, 100, R.FMT_ARGB, 60, dict(as_color=1, raw=1, xoffset=8, yoffset=2), dict(black_point=3, white_point=90)),
-    (753, 240, R.FMT_ABGR, 753, 236, R.FMT_RGBA, 5, dict(as_color=0), dict(brightness=9, contrast=200)),
-    (640, 480, R.FMT_BGRA, 640, 480, R.FMT_BGRA, 30, dict(as_color=1), dict(saturation=900, contrast=300)),
-]
-
-
 @pytest.mark.parametrize("fused", [False, True])
 @pytest.mark.parametrize("case", range(len(F4_CASES)))
-@pytest.mark.parametrize("name", ["snes", "temp", "pv1k"])
+@pytest.mark.parametrize("name", P.F4_NAMES)
 def test_f4_systems_parity(crtlib, name, case, fused):
     """crt_snes.c / crt_template.c / crt_pv1k.c + the shared decoder (PV-1000: the 5-sample branch,
     crt_core.c:480-510,544-549).  Even cases run the lane-per-scanline decoder, odd ones the scanline-parallel one."""
     shape = 2 if case % 2 else 1
-    _run_case(crtlib, (name,) + F4_CASES[case], fused=fused, shape=shape, steps=3)
+    _run_case(crtlib, (name,) + F4_CASES[case], fused=fused, shape=shape, steps=3, table="F4_CASES")
 
 
 @pytest.mark.parametrize("fused", [False, True])
-@pytest.mark.parametrize("knobs", [dict(saturation=3), dict(saturation=7, contrast=250), dict(saturation=12, brightness=40),
-                                   dict(saturation=18), dict(saturation=30, contrast=20000), dict(saturation=-9), dict(saturation=200)])
+@pytest.mark.parametrize("knobs", P.PV1K_TIER_KNOBS)
 def test_pv1k_decoder_tiers(crtlib, knobs, fused):
     """round 3: the 5-sample system in every decoder tier -- its five carriers are bounded by (|dci| + |dcq| + 1) * |saturation|
     (crt_core.c:497-505), which opens the 64-bit-mad and 24-bit tiers for it; the saturation walks through all of them"""
-    case = ("pv1k", 640, 480, R.FMT_BGRA, 640, 480, R.FMT_BGRA, 24, dict(as_color=1, hue=11), dict(knobs, scanlines=1))
-    _run_case(crtlib, case, fused=fused, shape=1, steps=3)
+    _run_case(crtlib, P.pv1k_tier_case(knobs), fused=fused, shape=1, steps=3, table="PV1K_TIERS")
 
 
 @pytest.mark.parametrize("shape", [1, 2])
 @pytest.mark.parametrize("fused", [False, True])
-@pytest.mark.parametrize("case", [1, 3, 7, 8])
-@pytest.mark.parametrize("name", ["vhslcg", "ntscnovsync", "ntscnohsync", "ntschipass"])
+@pytest.mark.parametrize("case", P.VARIANT_CASES)
+@pytest.mark.parametrize("name", P.VARIANT_NAMES)
 def test_build_time_variants_parity(crtlib, name, case, fused, shape):
     """VERDICT round 2, missing #3: the reference's remaining #define switches as crthip_params.flags -- CRT_VHS_NOISE 0
     (crt_ntscvhs.h:29), CRT_DO_VSYNC 0 / CRT_DO_HSYNC 0 (crt_core.h:71-72; crt_core.c:323-341, 446-450), HIPASS 1
     (crt_ntsc.c:115-126) -- against the oracle's switches, which tests/test_oracle_vs_ref.py pins to the rebuilt reference"""
-    _run_case(crtlib, (name,) + CASES[case][1:], fused=fused, shape=shape, steps=3)
+    _run_case(crtlib, P.renamed(name, CASES[case]), fused=fused, shape=shape, steps=3, table="BUILD_VARIANTS")
 
 
-@pytest.mark.parametrize("sat", [11, 15, 17, 19, 22])
+@pytest.mark.parametrize("sat", P.ENVELOPE_SATURATIONS)
 def test_ntsc_between_the_envelopes(crtlib, sat):
     """saturation 10 gives |wave| ~ 48 000: 15 ... 22 crosses 65 532 (products), the signal-range bound of the fused path
     (no low cascades) and 120 000 (64-bit-mad tiers) -- fused and stage-level launches take different tiers here and must
     agree with the oracle all the same"""
-    case = ("ntsc", 640, 480, R.FMT_BGRA, 640, 480, R.FMT_BGRA, 24, dict(as_color=1), dict(saturation=sat, scanlines=1))
-    _run_case(crtlib, case, fused=True, shape=1, steps=3)
-    _run_case(crtlib, case, fused=False, shape=1, steps=2)
+    case = P.between_the_envelopes_case(sat)
+    _run_case(crtlib, case, fused=True, shape=1, steps=3, table="BETWEEN_ENVELOPES")
+    _run_case(crtlib, case, fused=False, shape=1, steps=2, table="BETWEEN_ENVELOPES")
 
 
 @pytest.mark.parametrize("fused", [False, True])
-@pytest.mark.parametrize("case", [0, 1, 2, 3, 4, 5])
-@pytest.mark.parametrize("name", ["ntscbloom", "snesbloom", "pv1kbloom"])
+@pytest.mark.parametrize("case", P.BLOOM_ROWS)
+@pytest.mark.parametrize("name", P.BLOOM_NAMES)
 def test_bloom_build_parity(crtlib, name, case, fused):
     """CRT_DO_BLOOM (crt_core.h:70 set to 1): encoder geometry 55500 / 63500 (crt_ntsc.c:148-161), per-line beam
     width -> per-line resampler step and start (crt_core.c:399-402, 512-526).  The oracle's bloom mode is pinned
     against the reference compiled with the patched header (tests/test_oracle_vs_ref.py)."""
-    _run_case(crtlib, (name,) + F4_CASES[case], fused=fused, shape=0, steps=3)
+    _run_case(crtlib, (name,) + F4_CASES[case], fused=fused, shape=0, steps=3, table="BLOOM")
 
 
 @pytest.mark.parametrize("fused", [False, True])
-@pytest.mark.parametrize("case", [0, 1, 2, 3, 4, 5])
-@pytest.mark.parametrize("name", ["ntscbloom", "snesbloom", "pv1kbloom"])
+@pytest.mark.parametrize("case", P.BLOOM_ROWS)
+@pytest.mark.parametrize("name", P.BLOOM_NAMES)
 def test_bloom_lane_per_scanline_parity(crtlib, name, case, fused):
     """the bloom build in the lane-per-scanline decoder (crt_decode3.hip) -- the lines of the batch are
     counting-sorted by their beam width (crt_core.c:518-522: dx and scanL follow from line_w alone), a wave decodes 64
     lines of equal geometry.  Forced here (shape 1); 5 fields = 1200 lines over a few dozen widths: full and partial
     waves, padding slots"""
-    _run_case(crtlib, (name,) + F4_CASES[case], fused=fused, shape=1, steps=2, n=5)
+    _run_case(crtlib, (name,) + F4_CASES[case], fused=fused, shape=1, steps=2, n=5, table="BLOOM")
 
 
-@pytest.mark.parametrize("knobs", [dict(saturation=14), dict(saturation=19), dict(saturation=40), dict(brightness=5000, contrast=20),
-                                   dict(saturation=900, contrast=300), dict(brightness=200000, contrast=9000000, white_point=9000000),
-                                   dict(blend=1, v_fac=30), dict(scanlines=1, blend=1)])
-@pytest.mark.parametrize("geom", [(640, 480, R.FMT_BGRA), (64, 48, R.FMT_RGB), (1920, 1080, R.FMT_RGBA), (100, 300, R.FMT_BGR)])
+@pytest.mark.parametrize("knobs", P.BLOOM_TIER_KNOBS)
+@pytest.mark.parametrize("geom", P.BLOOM_TIER_GEOMS)
 def test_bloom_lane_per_scanline_tiers_and_geometries(crtlib, knobs, geom):
     """the bloom kernel's tiers (0: 64-bit mads, 2: 24-bit mads -- also for the lines tier 1 would take --, 3: exact), the
     wide pixel tile (outw >= 1280), 3-byte formats, blend, and pictures shorter than the raster (several scanlines per
     output row, one decoder pass per collision rank)"""
-    outw, outh, ofmt = geom
-    case = ("ntscbloom", outw, outh, ofmt, 320, 240, R.FMT_BGRA, 24, dict(as_color=1, hue=33), knobs)
-    _run_case(crtlib, case, fused=True, shape=1, steps=2, n=3)
+    _run_case(crtlib, P.bloom_tier_case(knobs, geom), fused=True, shape=1, steps=2, n=3, table="BLOOM_TIERS")
 
 
 def test_bloom_decoder_takes_any_line_table(crtlib):
@@ -618,10 +560,8 @@ def test_rectangle_running_over_the_line_end(crtlib):
     xoffset 150 runs 147 samples into the next line -- over its sync pulse and burst: the ENCODER is still exact
     (analog[] compared); what the decoder makes of such a field involves windows far behind inp[] (reference UB)."""
     for fused in (False, True):
-        _run_case(crtlib, ("ntsc", 640, 480, R.FMT_BGRA, 640, 480, R.FMT_BGRA, 24, dict(as_color=1, xoffset=4), {}),
-                  fused=fused, steps=2)
-        _run_case(crtlib, ("ntsc", 640, 480, R.FMT_BGRA, 640, 480, R.FMT_BGRA, 0, dict(as_color=1, xoffset=16, yoffset=1), dict(scanlines=1)),
-                  fused=fused, steps=2, shape=2)
+        _run_case(crtlib, P.LINE_END_CASES[0], fused=fused, steps=2, table="LINE_END")
+        _run_case(crtlib, P.LINE_END_CASES[1], fused=fused, steps=2, shape=2, table="LINE_END")
     n, w, h = 2, 640, 480
     imgs = np.stack([R.synth_image(w, h, 4, 55 + k) for k in range(n)])
     g = crtlib.CRT(n, 640, 480, crtlib.FMT_BGRA, "ntsc", device=0)
@@ -658,58 +598,30 @@ def test_tight_images_are_never_read_past_their_end(crtlib):
     np.testing.assert_array_equal(outs[0], outs[1])
 
 
-NES_CASES = [
-    # name, outw, outh, noise, knobs
-    ("nes", 640, 480, 0, {}),
-    ("nes", 640, 480, 24, dict(scanlines=1)),
-    ("nesp0", 640, 480, 12, dict(blend=1, hue=15)),       # BASELINE configs[4]: CRT_CHROMA_PATTERN 0
-    ("nesp0", 256, 240, 0, dict(saturation=12)),
-    ("nes", 768, 720, 40, dict(scanlines=1, black_point=2, white_point=95)),
-    # round 3: either side of the decoder envelopes that follow from the NES's own signal range (carrier amplitude grows
-    # with the saturation: tier 0 -> tier 1 without / with the I/Q low cascades -> 24-bit tier)
-    ("nesp0", 640, 480, 12, dict(saturation=8)),
-    ("nesp0", 640, 480, 60, dict(saturation=13, scanlines=1)),
-    ("nesp0", 640, 480, 100, dict(saturation=16)),
-    ("nes", 640, 480, 30, dict(saturation=19, white_point=120)),
-    ("nes", 640, 480, 12, dict(saturation=26, contrast=40000)),
-    # NES_BORDER 1 (crt_nes.c:69,138-160): the border colour right of the picture
-    ("nesborder", 640, 480, 12, dict(scanlines=1)),
-    ("nesborder", 512, 480, 0, dict(black_point=4, white_point=90)),
-    # wide pictures: the wide-run decoder (crt_decode4.hip), which the NES enters in tier 1 (its carriers do not fit 24 bits)
-    ("nesp0", 1920, 1080, 12, dict(scanlines=1)),
-    ("nes", 1700, 600, 24, dict(saturation=16)),
-]
-
-
 @pytest.mark.parametrize("fused", [False, True])
 @pytest.mark.parametrize("case", range(len(NES_CASES)))
 def test_nes_parity(crtlib, case, fused):
     """NES encoder (crt_nes.c): 256x240 9-bit PPU pixels, 3-line chroma period, dot crawl."""
     import torch
     name, outw, outh, noise, knobs = NES_CASES[case]
-    n = 3
-    orc = R.Oracle(name)
+    n = P.NES_N
+    libs = _checkers(name)
+    orc = libs[0][1]
     g = crtlib.CRT(n, outw, outh, crtlib.FMT_BGRA, name, device=0)
     if outw >= 1664:
         g.set_shape(1)                       # three fields would otherwise take the scanline-parallel kernels
-    ocrts = [orc.new_crt(outw, outh, R.FMT_BGRA) for _ in range(n)]
+    crts = [[P.nes_checker_crt(lib, NES_CASES[case]) for _ in range(n)] for _, lib in libs]
     for k, v in knobs.items():
         setattr(g, k, v)
-        for c in ocrts:
-            c.set(k, v)
     s = None
-    for step in range(4):
-        ppu = np.stack([R.synth_ppu(256, 240, 31 * step + k) for k in range(n)])
+    for step in range(P.NES_STEPS):
+        ppu = np.stack([P.nes_ppu(step, k) for k in range(n)])
         full = torch.zeros((n, 241, 256), dtype=torch.int16, device="cuda:0")
         full[:, :240] = torch.from_numpy(ppu.astype(np.int16)).to("cuda:0")
-        dco = [(step + k) % 3 for k in range(n)]
+        kw = [P.nes_settings(step, k) for k in range(n)]
         init = s.initialized if s is not None else 0
-        border = [0x21, 0x16, 0x1c0 | 0x2a, 0x0d][step]
-        s = crtlib.Settings(full[:, :240], hue=(step * 50) % 360, dot_crawl_offset=dco, border_color=border)
+        s = crtlib.Settings(full[:, :240], hue=kw[0]["hue"], dot_crawl_offset=[q["dot_crawl_offset"] for q in kw], border_color=kw[0]["border_color"])
         s.initialized = init
-        for k, c in enumerate(ocrts):
-            pad = np.concatenate([ppu[k], ppu[k][-1:]], axis=0)
-            c.settings(pad, w=256, h=240, dot_crawl_offset=dco[k], hue=(step * 50) % 360, border_color=border)
         if fused:
             g.fieldpass(s, noise)
         else:
@@ -718,21 +630,17 @@ def test_nes_parity(crtlib, case, fused):
             g.demodulate(noise)
         g.synchronize()
         gout = g.out.cpu().numpy()
-        for k, c in enumerate(ocrts):
-            what = "%s fused=%s step %d field %d" % (name, fused, step, k)
-            if fused:
-                # the fused path starts every field from a crt_init-clean analog[] (documented batch
-                # semantics): mirror that in the oracle by re-running setup_field on a zeroed signal
-                c.analog[:] = 0
-                c.sset("field_initialized", 0)
-            c.modulate()
-            if not fused:
-                np.testing.assert_array_equal(analog[k, :orc.input_size], c.analog, err_msg=what + " analog")
-            c.demodulate(noise)
-            for f in ("hsync", "vsync", "rn"):
-                assert g.get(f)[k] == c.get(f), "%s %s" % (what, f)
-            np.testing.assert_array_equal(g.ccf[k, :orc.vper, :orc.ccs], c.ccf, err_msg=what + " ccf")
-            np.testing.assert_array_equal(gout[k].reshape(-1), c.out, err_msg=what + " out")
+        for (tag, lib), per in zip(libs, crts):
+            for k, c in enumerate(per):
+                what = "%s fused=%s step %d field %d, against the %s:" % (name, fused, step, k, tag)
+                P.nes_checker_pass(c, step, k, fused)          # (fused: from a crt_init-clean analog[], the documented batch semantics)
+                if not fused:
+                    np.testing.assert_array_equal(analog[k, :orc.input_size], c.analog, err_msg=what + " analog")
+                c.demodulate(noise)
+                for f in ("hsync", "vsync", "rn"):
+                    assert g.get(f)[k] == c.get(f), "%s %s" % (what, f)
+                np.testing.assert_array_equal(g.ccf[k, :orc.vper, :orc.ccs], c.ccf, err_msg=what + " ccf")
+                np.testing.assert_array_equal(gout[k].reshape(-1), c.out, err_msg=what + " out")
     g.close()
 
 
@@ -805,9 +713,9 @@ def test_vhs_encoder_parity(crtlib, aberration):
     g.close()
 
 
-@pytest.mark.parametrize("sysname", ["vhs", "vhsbloom", "vhslp", "vhsep"])
+@pytest.mark.parametrize("sysname", P.VHS_NAMES)
 @pytest.mark.parametrize("fused", [False, True])
-@pytest.mark.parametrize("noise", [0, 12, 40])
+@pytest.mark.parametrize("noise", P.VHS_NOISES)
 def test_vhs_fieldpass_parity(crtlib, fused, noise, sysname):
     _vhs_fieldpass(crtlib, fused, noise, sysname, 0)
 
@@ -820,37 +728,21 @@ def test_vhs_bloom_lane_per_scanline_parity(crtlib, fused):
 
 def test_vhs_wide_run_decoder_parity(crtlib):
     """the VHS build at 1920x1080 through the wide-run decoder (crt_decode4.hip)"""
-    _vhs_fieldpass(crtlib, True, 12, "vhs", 1, size=(1920, 1080))
+    _vhs_fieldpass(crtlib, True, 12, "vhs", 1, size=P.VHS_WIDE_SIZE)
 
 
-def _vhs_fieldpass(crtlib, fused, noise, sysname, shape, size=(832, 624)):
+def _vhs_fieldpass(crtlib, fused, noise, sysname, shape, size=P.VHS_SIZE):
     """BASELINE configs[3]: CRT_SYSTEM_NTSCVHS, 832x624 (and its CRT_DO_BLOOM build).  The decoder's noise is the C library's rand()
     stream (crt_core.c:344-351): field k's generator starts at srand(seed_k) and carries over from
-    step to step, so the oracle processes each field's whole sequence under its own libc stream.
+    step to step, so a checker processes each field's whole sequence under its own libc stream (parity_cases.vhs_sequence) -- the
+    oracle first, then the real reference under the same seed, never interleaved: they share the process's stream.
     (The aberration band draws from the same stream in crt_modulate; that interplay is covered by the
     drop-in test, where the host draws it exactly like the reference.)"""
-    import ctypes as C
-    libc = C.CDLL(None)
-    n, (w, h), steps = 3, size, 3
-    seeds = [1, 77, 20260924]
-    imgs = np.stack([R.synth_image(w, h, 4, 60 + k, "random" if k != 1 else "bars") for k in range(n)])
-    orc = R.Oracle(sysname)
-    want = []
-    for k in range(n):
-        c = orc.new_crt(w, h, R.FMT_BGRA)
-        c.set("scanlines", 1)
-        c.settings(np.concatenate([imgs[k], imgs[k][-1:]]), format=R.FMT_BGRA, w=w, h=h, as_color=1, field=k & 1, frame=0,
-                   do_aberration=0)
-        libc.srand(seeds[k])
-        per = []
-        for step in range(steps):
-            if fused:
-                c.analog[:] = 0                        # batch semantics: clean analog[] per field-pass
-            c.modulate()
-            c.demodulate(noise)
-            per.append((c.inp.copy(), c.out.copy(), c.get("hsync"), c.get("vsync"), c.get("rn"), c.ccf.copy()))
-            c.sset("field", c.sget("field") ^ 1)
-        want.append(per)
+    n, (w, h), steps, seeds = P.VHS_N, size, P.VHS_STEPS, P.VHS_SEEDS
+    imgs = P.vhs_images(size)
+    libs = _checkers(sysname)
+    orc = libs[0][1]
+    want = [[P.vhs_sequence(lib, sysname, fused, noise, size, k, imgs[k], stages=True) for k in range(n)] for _, lib in libs]
     g = crtlib.CRT(n, w, h, crtlib.FMT_BGRA, sysname, device=0)
     g.scanlines = 1
     g.set_shape(shape)
@@ -862,65 +754,54 @@ def _vhs_fieldpass(crtlib, fused, noise, sysname, shape, size=(832, 624)):
             g.fieldpass(s, noise)
         else:
             g.modulate(s)
+            ganalog = g.analog[:, :orc.input_size].cpu().numpy()
             g.demodulate(noise)
         g.synchronize()
         gout = g.out.cpu().numpy()
-        for k in range(n):
-            inp, out, hs, vs, rn, ccf = want[k][step]
-            what = "%s fused=%s noise %d step %d field %d" % (sysname, fused, noise, step, k)
-            if not fused:
-                np.testing.assert_array_equal(g.inp[k, :orc.input_size].cpu().numpy(), inp, err_msg=what + " inp")
-            assert (g.get("hsync")[k], g.get("vsync")[k], g.get("rn")[k]) == (hs, vs, rn), what
-            np.testing.assert_array_equal(g.ccf[k, :1, :4], ccf, err_msg=what + " ccf")
-            np.testing.assert_array_equal(gout[k].reshape(-1), out, err_msg=what + " out")
+        for (tag, _), per in zip(libs, want):
+            for k in range(n):
+                inp, out, hs, vs, rn, ccf, analog, _ = per[k][step]
+                what = "%s fused=%s noise %d step %d field %d, against the %s:" % (sysname, fused, noise, step, k, tag)
+                if not fused:
+                    np.testing.assert_array_equal(ganalog[k], analog, err_msg=what + " analog")
+                    np.testing.assert_array_equal(g.inp[k, :orc.input_size].cpu().numpy(), inp, err_msg=what + " inp")
+                assert (g.get("hsync")[k], g.get("vsync")[k], g.get("rn")[k]) == (hs, vs, rn), what
+                np.testing.assert_array_equal(g.ccf[k, :1, :4], ccf, err_msg=what + " ccf")
+                np.testing.assert_array_equal(gout[k].reshape(-1), out, err_msg=what + " out")
         fields = [f ^ 1 for f in fields]
         s.field = list(fields)
     g.close()
 
 
-@pytest.mark.parametrize("noise", [7, 100])
+@pytest.mark.parametrize("noise", P.MANY_SEEDS_NOISES)
 def test_vhs_rand_noise_many_seeds(crtlib, noise):
     """The data-dependent part of the VHS rand() walk (last 25 lines: 2 or 3 calls per sample) under many
     generator seeds, two crt_demodulate calls in a row so that the second one
-    starts from the history the first one hands back.  Checked: inp[], rn, hsync/vsync and the picture."""
-    import ctypes as C
+    starts from the history the first one hands back.  Checked: inp[], rn, hsync/vsync and the picture -- against the oracle and,
+    seed by seed and sequentially like it, against the real reference."""
     import torch
-    libc = C.CDLL(None)
-    n, w, h = 40, 96, 240
-    seeds = [1 + 7919 * k for k in range(n)]
-    orc = R.Oracle("vhs")
-    # a properly encoded field (the decoder must find its sync pulses, or it reads past inp[] like the reference
-    # would), the same for every seed
-    img = R.synth_image(w, h, 4, 4242)
-    c0 = orc.new_crt(w, h, R.FMT_BGRA)
-    c0.settings(np.concatenate([img, img[-1:]]), format=R.FMT_BGRA, w=w, h=h, as_color=1, field=0, frame=0, do_aberration=0)
-    c0.modulate()
-    analog = np.repeat(c0.analog.copy()[None, :], n, axis=0)
+    n, (w, h), seeds = P.MANY_SEEDS_N, P.MANY_SEEDS_SIZE, P.MANY_SEEDS
+    libs = _checkers("vhs")
+    orc = libs[0][1]
+    one = P.many_seeds_analog(orc)
+    analog = np.repeat(one[None, :], n, axis=0)
     g = crtlib.CRT(n, w, h, crtlib.FMT_BGRA, "vhs", device=0)
     g.srand(seeds)
     g.analog[:, :orc.input_size].copy_(torch.from_numpy(analog).to(g.dev))
-    want = []
-    for k in range(n):
-        c = orc.new_crt(w, h, R.FMT_BGRA)
-        c.analog[:] = analog[k]
-        libc.srand(seeds[k])
-        per = []
-        for step in range(2):
-            c.demodulate(noise)
-            per.append((c.inp.copy(), c.out.copy(), c.get("hsync"), c.get("vsync"), c.get("rn")))
-        want.append(per)
+    want = [[P.many_seeds_sequence(lib, one, noise, k) for k in range(n)] for _, lib in libs]
     for step in range(2):
         g.demodulate(noise)
         g.synchronize()
         ginp = g.inp[:, :orc.input_size].cpu().numpy()
         gout = g.out.cpu().numpy()
-        for k in range(n):
-            inp, out, hs, vs, rn = want[k][step]
-            what = "seed %d noise %d call %d" % (seeds[k], noise, step)
-            bad = np.nonzero(ginp[k] != inp)[0]
-            assert bad.size == 0, "%s: inp differs first at sample %d (of %d)" % (what, bad[0], orc.input_size)
-            assert (g.get("hsync")[k], g.get("vsync")[k], g.get("rn")[k]) == (hs, vs, rn), what
-            np.testing.assert_array_equal(gout[k].reshape(-1), out, err_msg=what)
+        for (tag, _), per in zip(libs, want):
+            for k in range(n):
+                inp, out, hs, vs, rn = per[k][step]
+                what = "seed %d noise %d call %d, against the %s" % (seeds[k], noise, step, tag)
+                bad = np.nonzero(ginp[k] != inp)[0]
+                assert bad.size == 0, "%s: inp differs first at sample %d (of %d)" % (what, bad[0], orc.input_size)
+                assert (g.get("hsync")[k], g.get("vsync")[k], g.get("rn")[k]) == (hs, vs, rn), what
+                np.testing.assert_array_equal(gout[k].reshape(-1), out, err_msg=what)
     g.close()
 
 
@@ -1115,69 +996,30 @@ def test_tuning_switches_do_not_change_results(crtlib, overlap, tile):
         np.testing.assert_array_equal(outs[1][0][k].reshape(-1), c.out, err_msg="field %d" % k)
 
 
-def _random_case(rng):
-    w = int(rng.choice([1, 2, 3, 5, 17, 64, 100, 333, 640, 753, 800, 1281]))
-    h = int(rng.choice([1, 2, 7, 48, 100, 236, 237, 480, 601]))
-    outw = int(rng.choice([1, 3, 4, 5, 31, 32, 33, 250, 640, 1283]))
-    outh = int(rng.choice([1, 17, 120, 239, 240, 241, 480, 500, 777]))
-    ifmt, ofmt = int(rng.integers(0, 6)), int(rng.integers(0, 6))
-    raw = int(rng.integers(0, 2))
-    skw = dict(as_color=int(rng.integers(0, 2)), raw=raw, hue=int(rng.integers(-400, 800)))
-    if raw and w <= 640 and h <= 200:
-        # offsets only where the active rectangle still fits the raster: beyond that crt_modulate scribbles
-        # over neighbouring lines (crt_ntsc.c:322) -- outside the contract, the library refuses it
-        skw.update(xoffset=int(rng.integers(0, 3)) * 4, yoffset=int(rng.integers(0, 3)))
-    knobs = dict(hue=int(rng.integers(-360, 720)), brightness=int(rng.integers(-40, 40)), contrast=int(rng.integers(0, 400)),
-                 saturation=int(rng.integers(-5, 40)), black_point=int(rng.integers(-10, 10)),
-                 white_point=int(rng.integers(50, 150)), scanlines=int(rng.integers(0, 2)), blend=int(rng.integers(0, 2)),
-                 v_fac=int(rng.choice([0, 0, 0, 7, 100])))
-    noise = int(rng.choice([0, 1, 24, 77, 300]))
-    return ("ntsc", outw, outh, ofmt, w, h, ifmt, noise, skw, knobs)
-
-
-def _random_wide_case(rng):
-    """_random_case with picture widths the wide-run decoder takes (crt_decode4.hip: outw from ~1650 up, 4-byte pixels, no blend);
-    three-byte formats, blend and the narrower widths in the list fall back to the lane-per-scanline kernel -- also a case"""
-    case = list(_random_case(rng))
-    case[0] = str(rng.choice(["ntsc", "ntscp0", "snes", "temp", "nesrgb"]))
-    case[1] = int(rng.choice([1500, 1650, 1664, 1700, 1919, 1920, 1921, 2047, 2560, 3001, 3840, 4095]))
-    case[2] = int(rng.choice([1, 120, 240, 241, 480, 777, 1080, 1200, 2160]))
-    case[3] = int(rng.choice([R.FMT_RGBA, R.FMT_BGRA, R.FMT_ARGB, R.FMT_ABGR, R.FMT_RGBA, R.FMT_BGRA, R.FMT_RGB]))
-    case[9] = dict(case[9], blend=int(rng.integers(0, 8) == 0))
-    return tuple(case)
-
-
 @pytest.mark.parametrize("lpw", [8, 16])
-@pytest.mark.parametrize("seed", range(16))
+@pytest.mark.parametrize("seed", range(P.RANDOM_WIDE_SEEDS))
 def test_random_wide_configurations(crtlib, seed, lpw):
     """random wide pictures, knobs, formats and systems through the lane shape (wide-run decoder where it applies), with each of
     its two instantiations pinned"""
-    rng = np.random.default_rng(7000 + seed)
-    _run_case(crtlib, _random_wide_case(rng), fused=bool(seed & 1), steps=2, n=2, shape=1, wide_lpw=lpw)
+    _run_case(crtlib, P.random_wide_seed_case(seed), fused=bool(seed & 1), steps=2, n=2, shape=1, wide_lpw=lpw, table="RANDOM_WIDE")
 
 
-@pytest.mark.parametrize("seed", range(48))
+@pytest.mark.parametrize("seed", range(P.RANDOM_SEEDS))
 def test_random_configurations(crtlib, seed):
     """odd / tiny / large geometries, all format pairs, random knobs: stagewise AND fused, 2 steps each"""
-    rng = np.random.default_rng(1000 + seed)
-    case = _random_case(rng)
-    _run_case(crtlib, case, fused=bool(seed & 1), steps=2, n=2, shape=1)
+    _run_case(crtlib, P.random_seed_case(seed), fused=bool(seed & 1), steps=2, n=2, shape=1, table="RANDOM")
 
 
-@pytest.mark.parametrize("seed", range(48))
+@pytest.mark.parametrize("seed", range(P.RANDOM_SEEDS))
 def test_random_configurations_scanline_parallel_shape(crtlib, seed):
     """the same random configurations forced onto the scanline-parallel kernels"""
-    rng = np.random.default_rng(1000 + seed)
-    case = _random_case(rng)
-    _run_case(crtlib, case, fused=bool(seed & 1), steps=2, n=2, shape=2)
+    _run_case(crtlib, P.random_seed_case(seed), fused=bool(seed & 1), steps=2, n=2, shape=2, table="RANDOM")
 
 
-@pytest.mark.parametrize("seed", range(24))
+@pytest.mark.parametrize("seed", range(P.RANDOM_BLOOM_SEEDS))
 def test_random_configurations_bloom_lane_per_scanline(crtlib, seed):
     """random configurations of the bloom builds through the beam-width sort + lane-per-scanline decoder"""
-    rng = np.random.default_rng(5000 + seed)
-    case = ("ntscbloom", "snesbloom", "pv1kbloom")[seed % 3], *_random_case(rng)[1:]
-    _run_case(crtlib, case, fused=bool(seed & 1), steps=2, n=3, shape=1)
+    _run_case(crtlib, P.random_bloom_seed_case(seed), fused=bool(seed & 1), steps=2, n=3, shape=1, table="RANDOM_BLOOM")
 
 
 @pytest.mark.parametrize("name,n,w,h,noise", [("ntsc", 4096, 640, 480, 24), ("ntsc", 64, 1920, 1080, 0), ("ntsc", 512, 1920, 1080, 0),
@@ -1411,8 +1253,7 @@ def test_a_kept_nes_graph_keeps_both_of_its_tables(crtlib):
     g.close()
 
 
-@pytest.mark.parametrize("name,n,noise,fpb4", [("ntsc", 24, 0, 0), ("ntsc", 24, 150, 0), ("ntsc", 520, 60, 1), ("snes", 24, 100, 0), ("pv1k", 12, 90, 0),
-                                               ("nes", 24, 80, 0), ("ntscbloom", 24, 40, 0), ("ntsc", 24, 150, 1), ("snes", 24, 100, 1), ("nes", 24, 80, 1)])
+@pytest.mark.parametrize("name,n,noise,fpb4", P.WILD_PARAMS)
 def test_wild_sync_states_against_the_oracle(crtlib, name, n, noise, fpb4):
     """Fields started from sync states far from lock -- vertical sync candidates in the middle of the picture under heavy noise,
     hsync values that put the search window or the burst window into the picture, values near the line end (windows that wrap)
@@ -1426,22 +1267,11 @@ def test_wild_sync_states_against_the_oracle(crtlib, name, n, noise, fpb4):
     the fused path and are decoded from the per-field scratch copy (crt_sync.hip).
     (Rounds 4's speculative sync chain was tested with these inputs; the chain is gone, the inputs stayed.)"""
     import torch
-    nes = name == "nes"
-    w, h = (256, 240) if nes else (640, 480)
-    hs0 = [0, 3, 30, 60, 140, 300, 500, 700, 880, 892, 905, 909]
-    vs0 = [0, 4, 9, 100, 180, 250, 255, 258, 261]
-    uniq = min(n, 24)
-    if nes:
-        base = np.stack([R.synth_ppu(w, h, 8100 + k) for k in range(uniq)]).astype(np.int16)
-    else:
-        base = np.stack([R.synth_image(w, h, 4, 8100 + k, "bars" if k % 3 == 1 else "random") for k in range(uniq)])
-        base[2::3] //= 16                                  # dark pictures: a noisy candidate line crosses the threshold more easily
+    wild = P.wild_inputs(name, n)                          # the pictures and start states: tests/parity_cases.py
+    nes, h, uniq, base, hs, vs, fields = (wild[f] for f in ("nes", "h", "uniq", "base", "hs", "vs", "fields"))
     imgs = torch.from_numpy(np.concatenate([base, base[:, -1:]], axis=1)).to("cuda:0")
     reps = (n + uniq - 1) // uniq
     data = (imgs.repeat(reps, 1, 1) if nes else imgs.repeat(reps, 1, 1, 1))[:n, :h]
-    hs = [hs0[(k // uniq + k) % len(hs0)] for k in range(n)]
-    vs = [vs0[(k // uniq * 5 + k) % len(vs0)] for k in range(n)]
-    fields = [k & 1 for k in range(n)]
     outs = {}
     for spec in (1,):      # (one pass; the dict keeps the shape the comparisons below were written for)
         import os
@@ -1472,36 +1302,28 @@ def test_wild_sync_states_against_the_oracle(crtlib, name, n, noise, fpb4):
             per.append((g.out.cpu().numpy().copy(), g.state.cpu().numpy().copy()))
         outs[spec] = per
         g.close()
-    orc = R.Oracle(name)
-    check = range(n) if n <= 64 else list(range(0, n, 7)) + [n - 1]
+    libs = _checkers(name)                                 # the oracle, and the real reference where its build is there
+    orc = libs[0][1]
+    check = wild["check"]
     checked = 0
     for k in check:
-        c = orc.new_crt(640, 480, R.FMT_BGRA)
-        c.set("scanlines", 1)
-        c.set("hsync", hs[k])
-        c.set("vsync", vs[k])
-        pad = np.concatenate([base[k % uniq], base[k % uniq][-1:]])
-        if nes:
-            c.settings(pad.astype(np.uint16), w=w, h=h, dot_crawl_offset=k % 3, hue=0)
-        else:
-            c.settings(pad, format=R.FMT_BGRA, w=w, h=h, as_color=1, field=fields[k], frame=0)
-            if name in ("snes", "pv1k"):
-                c.sset("dot_crawl_offset", k % 3)
+        crts = [P.wild_checker_crt(lib, name, wild, k) for _, lib in libs]
         for step in range(3):
-            c.analog[:] = 0                                # batch semantics: every field-pass starts from a clean analog[]
-            if nes:
-                c.sset("field_initialized", 0)
-            c.modulate()
-            hs_before = c.get("hsync")
-            c.demodulate(noise, trace=True)
-            if R.reads_past_inp(orc, c.trace, c.get("vsync"), hs_before):
+            for c in crts:
+                P.wild_checker_modulate(c, nes)            # batch semantics: every field-pass starts from a clean analog[]
+            hs_before = crts[0].get("hsync")
+            crts[0].demodulate(noise, trace=True)
+            for c in crts[1:]:
+                c.demodulate(noise)
+            if R.reads_past_inp(orc, crts[0].trace, crts[0].get("vsync"), hs_before):
                 break                                      # the reference itself reads past inp[] + 16 here (sync far out on the field's last analog line): UB, not compared
             checked += 1
             st = outs[1][step][1][k]
-            what = "%s noise %d field %d (hsync0 %d vsync0 %d) step %d" % (name, noise, k, hs[k], vs[k], step)
-            assert (int(st[crtlib.ST_HSYNC]), int(st[crtlib.ST_VSYNC]), int(st[crtlib.ST_RN])) == (c.get("hsync"), c.get("vsync"), c.get("rn")), what
-            np.testing.assert_array_equal(st[crtlib.ST_CCF:crtlib.ST_CCF + 25].reshape(5, 5)[:orc.vper, :orc.ccs], c.ccf, err_msg=what + " ccf")
-            np.testing.assert_array_equal(outs[1][step][0][k].reshape(-1), c.out, err_msg=what + " out")
+            for (tag, _), c in zip(libs, crts):
+                what = "%s noise %d field %d (hsync0 %d vsync0 %d) step %d, against the %s" % (name, noise, k, hs[k], vs[k], step, tag)
+                assert (int(st[crtlib.ST_HSYNC]), int(st[crtlib.ST_VSYNC]), int(st[crtlib.ST_RN])) == (c.get("hsync"), c.get("vsync"), c.get("rn")), what
+                np.testing.assert_array_equal(st[crtlib.ST_CCF:crtlib.ST_CCF + 25].reshape(5, 5)[:orc.vper, :orc.ccs], c.ccf, err_msg=what + " ccf")
+                np.testing.assert_array_equal(outs[1][step][0][k].reshape(-1), c.out, err_msg=what + " out")
     assert checked >= 2 * len(list(check)), "too many fields fell into the reference's undefined behaviour to mean anything"
 
 
