@@ -271,6 +271,10 @@ int  crthip_reserve(crthip_ctx *ctx, int n_fields);
  *   d_recs     : n crthip_knob_rec, 32 bytes apart, 4-byte aligned, READ ONLY.
  *   d_levs     : n crthip_level_rec (crthip_bind_levels), 16 bytes apart, 4-byte aligned, READ ONLY; checked when it is bound.
  *   d_hues     : n crthip_hue_rec (crthip_bind_hues), 640 bytes apart, 4-byte aligned, READ ONLY; checked when it is bound.
+ *   d_srecs    : n crthip_size_rec (crthip_fieldpass_sizes / crthip_stills_sizes), 32 bytes apart, 4-byte aligned, READ ONLY.  In
+ *              those two calls d_images has no stride: image k = the w_k*h_k*bpp bytes from d_images + off_k (one more row with
+ *              CRTHIP_F_IMAGE_SPARE_ROW), READ ONLY, everything inside [d_images, d_images + crthip_sizes_env.extent); base and
+ *              offsets multiples of 4 for the 4-byte formats.
  *   d_hist     : n x 32 words (crthip_vhs_bind_history), 4-byte aligned; checked when it is bound.
  *   d_analog, d_inp, d_inp_flat : n fields crthip_field_stride() bytes apart, 4-byte aligned; ALL crthip_field_stride() bytes of a
  *              field belong to the library (CRT_INPUT_SIZE samples, the CRTHIP_TAIL mirror, slack the 16-byte pieces of the
@@ -589,6 +593,71 @@ int  crthip_stills_knobs(crthip_ctx *ctx, const crthip_params *p, int n,
                          void *d_out, size_t out_stride, crthip_state *d_state,
                          int n_passes, const crthip_pass *sched /* host */,
                          const crthip_knob_rec *d_recs /* n, DEVICE */, const crthip_knobs_env *env /* host */);
+
+/*
+ * MIXED IMAGE SIZES in one batch: every field with its own w, h and image -- a folder of photos, an augmentation set, a sprite sheet.
+ * With raw == 0 the signal geometry (destw, desth, xo, yo) does not depend on the image size; the size enters crt_modulate on the
+ * SOURCE side only: the column x * w / destw (crt_ntsc.c:278), the row y * h / desth + field_offset (:258-261), the clamp
+ * `if (sy >= h) sy = h` (:263) and the row pitch sy * w.  Margins, noise, sync chain, decoder, signal layout, skeleton cache and the
+ * 24-bit envelope are those of the uniform call.
+ *
+ * crthip_sizes_prepare (host only): sizes[k] = field k's w, h and the byte offset of its image from d_images (off_lo / off_hi) ->
+ * recs[k] = what the kernels read for field k -- col_step exactly as crthip_params_finalize derives col_step_lo / _hi for a copy of p
+ * with that w -- and env = the bounds over the batch: the smallest and largest w and h, and extent = the end of the furthest image
+ * (offset + w * h * bpp bytes, one more row with CRTHIP_F_IMAGE_SPARE_ROW).  p->w, p->h, p->col_step_* and image_stride are then
+ * ignored.  Offsets are free: images packed back to back, padded, in any order, or shared (two fields may name one offset).
+ * CRTHIP_E_ARG: p not finalized, n <= 0, a NULL pointer; a size crthip_params_finalize would refuse in that copy of p (w <= 0,
+ * h <= 0); an offset that is no multiple of 4 for the 4-byte formats; p->raw != 0 (the signal rectangle then depends on w and h);
+ * CRTHIP_SYSTEM_NES (its PPU encoder has no per-field instantiation); an input format crt_modulate refuses (no image is read then);
+ * a field whose crthip_signal_layout_query verdict differs from that of p itself (the "geometry does not move" premise, checked).
+ *
+ * crthip_fieldpass_sizes: bit for bit and state for state what n calls of crthip_fieldpass with n = 1 give, call k made with p->w,
+ * p->h and d_images replaced by field k's w, h and d_images + off_k, on field k's slice of d_out and d_state.  d_srecs: the n
+ * records of crthip_sizes_prepare, uploaded by the caller (DEVICE memory, read when the kernels run: a captured graph reads what the
+ * buffer holds at replay); senv: the same call's bounds, host.  Everything crthip_fieldpass accepts is accepted with the same meaning
+ * (every 4-sample system and the PV-1000, both chroma patterns and VHS noise models, bloom, FIR, the phosphor flags, blend, all six
+ * input formats, both signal layouts and the signal tiles, overlap chunks, graph capture after crthip_reserve: it allocates nothing
+ * and does not synchronise); crthip_fieldpass_signal works after it; what crthip_fieldpass refuses is refused.  Images are READ
+ * ONLY: image k = the w_k * h_k * bpp bytes from d_images + off_k, with CRTHIP_F_IMAGE_SPARE_ROW its own row h_k as well (what the
+ * reference reads for odd fields with h <= desth), without the flag not a byte behind an image.
+ * KERNEL SHAPE: a sizes call always takes the lane-per-scanline encoder (k_active's SZ instantiations), whatever crthip_set_shape
+ * says -- crthip_set_shape(ctx, 2) is a no-op for the ENCODER of a sizes call, not an error (the decoder follows it as always); the
+ * scanline-parallel encoder has no per-field-size instantiation.  Every field gets whole wavefronts: ceil(desth / 64) workgroups,
+ * the lanes beyond desth idle, so that w, h, col_step and the image base are wave-uniform and the cooperative tile path stays in use.
+ * TEMPLATE CHOICES that the uniform call takes from p->w come from the env's bounds, ONE launch per call: 4-byte pixels go through
+ * the cooperative LDS tiles iff senv->w_min >= 4 (else every lane reads its pixels bytewise), the wide image tile iff senv->w_min
+ * >= 1280 (every image then fills whole 128-byte lines).  Every choice gives identical bytes.
+ * ADDRESS SAFETY: unlike the knobs the size enters ADDRESSES.  The host checks what it can see -- the env; the records are device
+ * memory and may be rewritten between graph replays.  So every wavefront checks its field's record against the captured extent
+ * before it reads a pixel: w >= 1 (>= 4 on the tile path), h >= 1, off aligned for the format, off + (h [+ 1]) * w * bpp <= extent;
+ * a record that fails is replaced by the smallest image at offset 0 (unspecified samples, no access outside
+ * [d_images, d_images + extent)).  Rows are clamped to [0, h] and every source column to [0, w) of the record -- on BOTH sides, by one
+ * unsigned compare: col_step is not checked, a rewritten one may give any column, negative ones included, and none leaves the row.  Records rewritten between replays must stay inside the captured env to give the contract's pictures.
+ * REFUSED before anything is launched (CRTHIP_E_ARG, crthip_error_string says which; d_out and d_state untouched): an env whose
+ * magic or n does not match or whose bounds contradict each other, d_srecs off its 4-byte alignment, d_images off its 4-byte
+ * alignment for the 4-byte formats, p->raw != 0, CRTHIP_SYSTEM_NES, an input format crt_modulate refuses.
+ *
+ * crthip_stills_sizes: crthip_stills for stills of mixed sizes -- bit for bit and state for state what n_passes calls of
+ * crthip_fieldpass_sizes give on the same images, d_out, d_state and records, d_state[k].field / .frame / .aux set to sched[r] before
+ * call r.  It shares its body with crthip_stills: at noise 0 every distinct schedule entry is encoded once (still k's clean signal
+ * depends on ITS size, not on the pass), into the same workspace (crthip_stills_reserve).  Accepted and refused: what crthip_stills
+ * and crthip_fieldpass_sizes accept and refuse.  crthip_fieldpass_signal after the call is refused, as after crthip_stills.
+ * Nothing of either call survives it: every other entry point launches exactly the kernels it launched before.
+ * OUT OF SCOPE: sizes combined with knob records (crthip_fieldpass_knobs and its siblings keep one size per batch), NES,
+ * raw images, sequence mode, shard.py / crt_hip_node.h (a video has one size).
+ */
+typedef struct crthip_size      { int w, h; unsigned off_lo, off_hi; } crthip_size;                                          /* 16 bytes */
+typedef struct crthip_size_rec  { int w, h; unsigned col_step_lo, col_step_hi, off_lo, off_hi; int reserved[2]; } crthip_size_rec;   /* 32 bytes */
+typedef struct crthip_sizes_env { int magic, n, w_min, w_max, h_min, h_max; unsigned extent_lo, extent_hi; } crthip_sizes_env;
+int  crthip_sizes_prepare(const crthip_params *p, int n, const crthip_size *sizes,
+                          crthip_size_rec *recs /* n, host, out */, crthip_sizes_env *env);
+int  crthip_fieldpass_sizes(crthip_ctx *ctx, const crthip_params *p, int n, const void *d_images,
+                            void *d_out, size_t out_stride, crthip_state *d_state,
+                            const crthip_size_rec *d_srecs /* n, DEVICE */, const crthip_sizes_env *senv /* host */);
+int  crthip_stills_sizes(crthip_ctx *ctx, const crthip_params *p, int n, const void *d_images,
+                         void *d_out, size_t out_stride, crthip_state *d_state,
+                         int n_passes, const crthip_pass *sched /* host */,
+                         const crthip_size_rec *d_srecs /* n, DEVICE */, const crthip_sizes_env *senv /* host */);
 
 /*
  * The phases of crthip_sequence, for hosts that cut ONE video over several contexts / devices / processes

@@ -140,6 +140,27 @@ class HuesEnv(C.Structure):
     _fields_ = [("magic", C.c_int), ("n", C.c_int), ("reserved", C.c_int * 6)]
 
 
+class Size(C.Structure):
+    """crthip_size (include/crt_hip.h): one field's image size and the byte offset of its image from d_images, 16 bytes."""
+    _fields_ = [("w", C.c_int), ("h", C.c_int), ("off_lo", C.c_uint), ("off_hi", C.c_uint)]
+
+
+class SizeRec(C.Structure):
+    """crthip_size_rec (include/crt_hip.h): what the encoder's SZ kernels read per field, 32 bytes."""
+    _fields_ = [("w", C.c_int), ("h", C.c_int), ("col_step_lo", C.c_uint), ("col_step_hi", C.c_uint),
+                ("off_lo", C.c_uint), ("off_hi", C.c_uint), ("reserved", C.c_int * 2)]
+
+
+class SizesEnv(C.Structure):
+    """crthip_sizes_env (include/crt_hip.h): the bounds of one crthip_sizes_prepare call."""
+    _fields_ = [("magic", C.c_int), ("n", C.c_int), ("w_min", C.c_int), ("w_max", C.c_int), ("h_min", C.c_int),
+                ("h_max", C.c_int), ("extent_lo", C.c_uint), ("extent_hi", C.c_uint)]
+
+    extent = property(lambda self: (self.extent_hi << 32) | self.extent_lo)     # bytes of the image buffer the call may read
+
+
+SIZE_REC_INTS = C.sizeof(SizeRec) // 4
+SZ_W, SZ_H, SZ_STEP_LO, SZ_STEP_HI, SZ_OFF_LO, SZ_OFF_HI = range(6)            # columns of the (n, 8) size record array
 LEVEL_REC_INTS = C.sizeof(LevelRec) // 4
 HUE_REC_INTS = C.sizeof(HueRec) // 4
 HUE_BURST, HUE_MODI, HUE_MODQ = 0, CARRIER_ROWS * MAX_CCS, 2 * CARRIER_ROWS * MAX_CCS    # first column of each table in the (n, 160) array
@@ -276,6 +297,10 @@ def load_library():
         L.crthip_bind_hues.argtypes = [vp, vp, C.POINTER(HuesEnv)]
     if hasattr(L, "crthip_stills_knobs"):                         # (likewise)
         L.crthip_stills_knobs.argtypes = [vp, PP, ci, vp, sz, vp, sz, vp, ci, C.POINTER(Pass), vp, C.POINTER(KnobsEnv)]
+    if hasattr(L, "crthip_fieldpass_sizes"):                      # (likewise)
+        L.crthip_sizes_prepare.argtypes = [PP, ci, C.POINTER(Size), C.POINTER(SizeRec), C.POINTER(SizesEnv)]
+        L.crthip_fieldpass_sizes.argtypes = [vp, PP, ci, vp, vp, sz, vp, vp, C.POINTER(SizesEnv)]
+        L.crthip_stills_sizes.argtypes = [vp, PP, ci, vp, vp, sz, vp, ci, C.POINTER(Pass), vp, C.POINTER(SizesEnv)]
     _LIB = L
     return L
 
@@ -398,6 +423,31 @@ def knobs_prepare8(params, knobs):
     return recs, levs, hues, env, lenv, henv
 
 
+def sizes_prepare(params, sizes):
+    """crthip_sizes_prepare (host only): ``sizes`` = (n, 3) integers, one (w, h, byte offset of the image from the buffer's start)
+    per field, for the finalized ``params`` (whose own w and h are ignored) -> (records as an (n, 8) uint32 numpy array in the
+    layout of SizeRec, SizesEnv)."""
+    import numpy as np
+    if hasattr(sizes, "detach"):
+        sizes = sizes.detach().cpu().numpy()
+    k = np.asarray(sizes)
+    if k.ndim != 2 or k.shape[1] != 3 or k.shape[0] < 1 or not np.issubdtype(k.dtype, np.integer):
+        raise ValueError("sizes must be an (n, 3) integer array of (w, h, byte offset)")
+    n = int(k.shape[0])
+    if (k[:, 2] < 0).any() or (np.abs(k[:, :2].astype(np.int64)) >= 1 << 31).any():
+        raise ValueError("sizes: w and h are 32-bit integers, offsets are not negative")
+    sin = (Size * n)()
+    for i in range(n):
+        off = int(k[i, 2])
+        sin[i].w, sin[i].h, sin[i].off_lo, sin[i].off_hi = int(k[i, 0]), int(k[i, 1]), off & 0xffffffff, off >> 32
+    recs = np.zeros((n, SIZE_REC_INTS), dtype=np.uint32)
+    env = SizesEnv()
+    rc = load_library().crthip_sizes_prepare(C.byref(params), n, sin, recs.ctypes.data_as(C.POINTER(SizeRec)), C.byref(env))
+    if rc:
+        raise ValueError("crthip_sizes_prepare failed (%d)" % rc)
+    return recs, env
+
+
 def _is_knobs8(knobs):
     import numpy as np
     k = knobs.detach().cpu().numpy() if hasattr(knobs, "detach") else np.asarray(knobs)
@@ -481,6 +531,9 @@ class CRT:
         self._levels_bound = False
         self.hue_recs = None       # device hue records of an (n, 8) upload_knobs ([n, 160] int32), bound likewise
         self._hues_bound = False
+        self.size_recs = None      # device size records of fieldpass_sizes / stills_sizes ([n, 8] int32, allocated by the first upload_sizes)
+        self._size_env = None
+        self._size_buf = None      # ... and the image buffer they describe
         self.use_stream(None)
         self.vhs_hist = None
         if self.sysid == SYSTEM_VHS:
@@ -690,6 +743,104 @@ class CRT:
                                            self.out.stride(0), C.c_void_p(self.state.data_ptr()),
                                            C.c_void_p(self.knob_recs.data_ptr()), C.byref(self._knob_env))
         self._check(rc, "crthip_fieldpass_knobs")
+        s.initialized = 1
+
+    # ------------------------------------------------------------------ mixed image sizes
+    def sizes_params(self, s, noise=0, flags=0):
+        """The parameter blob of a sizes call for settings ``s`` (format, as_color, hue, offsets; ``s.data`` is not used and may be
+        None; ``s.spare_row``: every image is followed by its own spare row): w and h are placeholders, the records carry them."""
+        flags |= self.eq_fir << 8
+        if self.phosphor not in PHOSPHOR_FLAGS:
+            raise ValueError("CRT.phosphor must be one of %s, not %r" % (sorted(PHOSPHOR_FLAGS), self.phosphor))
+        flags |= PHOSPHOR_FLAGS[self.phosphor]
+        if s.spare_row:
+            flags |= F_IMAGE_SPARE_ROW
+        if self.sysid in (SYSTEM_NES, SYSTEM_NESRGB) and not s.initialized:
+            flags |= F_NES_SETUP
+        return make_params(self.system, w=1, h=1, format=s.format, raw=s.raw, as_color=s.as_color, hue=s.hue,
+                           xoffset=s.xoffset, yoffset=s.yoffset, outw=self.outw, outh=self.outh,
+                           out_format=self.out_format, mon_hue=self.hue, brightness=self.brightness,
+                           contrast=self.contrast, saturation=self.saturation, black_point=self.black_point,
+                           white_point=self.white_point, scanlines=self.scanlines, blend=self.blend,
+                           v_fac=self.v_fac, noise=noise, flags=flags)
+
+    def pack_images(self, images, params):
+        """A list of n device tensors of shape (h_k [+ 1], w_k[, bpp]) uint8 -> (one uint8 buffer holding them back to back, at
+        offsets rounded up to 4 bytes for the 4-byte formats, an (n, 3) int64 array of (w, h, offset)).  With
+        CRTHIP_F_IMAGE_SPARE_ROW in ``params`` every tensor carries its spare row: h_k + 1 rows."""
+        import numpy as np
+        torch = self.torch
+        bpp = params.in_bpp
+        spare = 1 if params.flags & F_IMAGE_SPARE_ROW else 0
+        sizes = np.zeros((len(images), 3), dtype=np.int64)
+        off = 0
+        for k, t in enumerate(images):
+            if t.dtype != torch.uint8 or t.dim() not in (2, 3) or (t.dim() == 3 and t.shape[2] != bpp) or t.shape[0] <= spare:
+                raise ValueError("image %d: a uint8 tensor of shape (h%s, w, %d) is needed, not %s %s"
+                                 % (k, " + 1" if spare else "", bpp, t.dtype, tuple(t.shape)))
+            w = int(t.shape[1]) if t.dim() == 3 else int(t.shape[1]) // bpp
+            if bpp == 4:
+                off = (off + 3) & ~3
+            sizes[k] = (w, int(t.shape[0]) - spare, off)
+            off += t.numel()
+        buf = torch.empty((max(off, 1),), dtype=torch.uint8, device=self.dev)
+        for k, t in enumerate(images):
+            buf[int(sizes[k, 2]):int(sizes[k, 2]) + t.numel()] = t.to(self.dev).reshape(-1)
+        return buf, sizes
+
+    def upload_sizes(self, images, params):
+        """``images`` = a LIST of device tensors (pack_images packs them) or a TUPLE (uint8 device buffer, (n, 3) integer array of
+        (w, h, byte offset)): sizes_prepare for ``params`` + one copy into this CRT's device record buffer (allocated once, then
+        reused: a captured fieldpass_sizes reads what the buffer holds at replay).  Returns the SizesEnv."""
+        torch = self.torch
+        if isinstance(images, tuple):                              # (a tuple is always the pair; several images come as a list)
+            buf, sizes = images
+        else:
+            buf, sizes = self.pack_images(list(images), params)
+        recs, env = sizes_prepare(params, sizes)
+        if recs.shape[0] != self.n:
+            raise ValueError("%d sizes for a batch of %d fields" % (recs.shape[0], self.n))
+        if buf.dtype != torch.uint8 or not buf.is_contiguous() or buf.device != self.dev or buf.numel() < env.extent:
+            raise ValueError("the image buffer must be a contiguous uint8 tensor on %s of at least %d bytes" % (self.dev, env.extent))
+        if self.size_recs is None:
+            self.size_recs = torch.zeros((self.n, SIZE_REC_INTS), dtype=torch.int32, device=self.dev)
+        self.size_recs.copy_(torch.from_numpy(recs.view("int32")))
+        self._size_env, self._size_buf = env, buf
+        return env
+
+    def fieldpass_sizes(self, images, noise, params=None, settings=None):
+        """fieldpass for a batch of MIXED image sizes (crthip_fieldpass_sizes): ``images`` as for upload_sizes (None: the buffer,
+        records and bounds of the last upload_sizes -- inside a graph capture, where nothing may be copied from the host).
+        ``settings``: a Settings whose format / as_color / hue / offsets / field / frame / spare_row apply (its ``data`` is not
+        used; default Settings(None)); ``params``: a blob of sizes_params instead (the field state is then the caller's)."""
+        s = settings if settings is not None else Settings(None)
+        p = params if params is not None else self.sizes_params(s, noise)
+        if params is None:
+            self._load_field_state(s)
+        if images is not None:
+            self.upload_sizes(images, p)
+        if self.size_recs is None:
+            raise ValueError("fieldpass_sizes(None, ...): no sizes uploaded yet (upload_sizes)")
+        rc = self.L.crthip_fieldpass_sizes(self.ctx, C.byref(p), self.n, C.c_void_p(self._size_buf.data_ptr()),
+                                           C.c_void_p(self.out.data_ptr()), self.out.stride(0), C.c_void_p(self.state.data_ptr()),
+                                           C.c_void_p(self.size_recs.data_ptr()), C.byref(self._size_env))
+        self._check(rc, "crthip_fieldpass_sizes")
+        s.initialized = 1
+
+    def stills_sizes(self, images, noise, interlaced=True, first_field=0, frames=4, schedule=None, params=None, settings=None):
+        """stills for images of MIXED sizes (crthip_stills_sizes): ``images`` / ``settings`` / ``params`` as for fieldpass_sizes,
+        the schedule as for stills().  At noise 0 every distinct schedule entry is encoded once."""
+        buf = self._stills_passes(interlaced, first_field, frames, schedule)
+        s = settings if settings is not None else Settings(None)
+        p = params if params is not None else self.sizes_params(s, noise)
+        if images is not None:
+            self.upload_sizes(images, p)
+        if self.size_recs is None:
+            raise ValueError("stills_sizes(None, ...): no sizes uploaded yet (upload_sizes)")
+        rc = self.L.crthip_stills_sizes(self.ctx, C.byref(p), self.n, C.c_void_p(self._size_buf.data_ptr()),
+                                        C.c_void_p(self.out.data_ptr()), self.out.stride(0), C.c_void_p(self.state.data_ptr()),
+                                        len(buf), buf, C.c_void_p(self.size_recs.data_ptr()), C.byref(self._size_env))
+        self._check(rc, "crthip_stills_sizes")
         s.initialized = 1
 
     def stills_reserve(self, n_distinct):

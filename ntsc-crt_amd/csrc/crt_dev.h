@@ -497,6 +497,24 @@ __device__ __forceinline__ const crthip_hue_rec *hue_blob_recs(const crthip_para
     return (const crthip_hue_rec *) (((unsigned long long) (unsigned) P.burst[0][1] << 32) | (unsigned) P.burst[0][0]);
 }
 
+/* Mixed image sizes (crthip_sizes_prepare, crthip_fieldpass_sizes / crthip_stills_sizes): w, h, col_step and the image's offset per
+ * field.  The lane-per-row active-video kernel has a further instantiation, SZ, that takes them from the field's crthip_size_rec.
+ * No signature changes: a sizes call carries no knob records (crt_hip.h, OUT OF SCOPE), so the blob's `reserved` words carry the
+ * device pointer to the size record of the launch's field 0 exactly as they carry the knob records' in a knob call, and the
+ * `istride` argument of the launch -- a sizes call has no image stride -- carries the extent of the image buffer, against which
+ * every wavefront checks its record (size_rec_checked).  crthip_ctx.size_recs != nullptr says that such a call is under way. */
+static_assert(sizeof(crthip_size_rec) == 32 && sizeof(crthip_size) == 16, "crthip_size_rec: 32 bytes, crthip_size: 16");
+static inline void size_blob_set(crthip_params *q, const crthip_size_rec *d_srecs)
+{
+    static_assert(sizeof(q->reserved) == sizeof(d_srecs), "a device pointer fits crthip_params.reserved");
+    memcpy(q->reserved, &d_srecs, sizeof(d_srecs));
+}
+__device__ __forceinline__ const crthip_size_rec *size_blob_recs(const crthip_params &P)
+{
+    return (const crthip_size_rec *) (((unsigned long long) (unsigned) P.reserved[1] << 32) | (unsigned) P.reserved[0]);
+}
+#include "crt_size_guard.h"     /* size_view, size_rec_checked, size_col_clamped: plain C++, also compiled for the host by tests/test_sizes_cpu.py */
+
 /* Picture knobs (crthip_knobs_prepare5): is a call with such records under way?  The decoders then launch their PK instantiations */
 static inline bool knob_pic_call(const crthip_ctx *c);
 /* the tier flags a field's floor (crthip_knob_rec.tier_floor: 0, 2 or 3) puts on each of its lines -- what the decoders (and, min_tier >= 4,
@@ -673,6 +691,8 @@ struct crthip_ctx {
     crthip_hues_env hue_env;                /* ... and the library's copy of their env */
     int hue_on;                             /* the knob call under way runs with them: the encoder launches its HU instantiations */
     int hue_burst0[2];                      /* ... and the caller's burst[0][0..1], which the records' pointer replaced in the blob (hue_blob_set) */
+    const crthip_size_rec *size_recs;       /* a *_sizes call under way: the caller's device size records (field 0 of the call), else nullptr */
+    crthip_sizes_env size_env;              /* ... and the library's copy of their bounds: what the encoder's launch code decides by in place of p->w */
     hipStream_t aux_stream;
     hipEvent_t ev_fork, ev_join, ev_chunk[CRTHIP_MAX_CHUNKS];
     hipEvent_t ev_mfork, ev_mjoin;   /* the margin kernel beside the active-video kernel (crt_encode.hip, launch_encoder) */

@@ -414,18 +414,23 @@ struct RowTiles {
 /* source image row of destination row y: crt_ntsc.c:256-263 (field_offset where the system has one),
  * crt_nes.c:165-168 / crt_nesrgb.c:94-97 (NES timing).  The reference's `if (sy >= h) sy = h` (sic) addresses the
  * row BEHIND the image; that row is only read when the caller vouches for it (CRTHIP_F_IMAGE_SPARE_ROW). */
-template <class S> __device__ __forceinline__ int source_row(const crthip_params &P, int y, int field)
+/* (h: P.h, or the height of the lane's field in a sizes call -- the SZ instantiations of k_active) */
+template <class S> __device__ __forceinline__ int source_row(const crthip_params &P, int h, int y, int field)
 {
     int sy;
     if constexpr (S::NES_TIMING) {
-        sy = (y * P.h) / S::LINES;
+        sy = (y * h) / S::LINES;
     } else {
-        const int field_offset = S::FIELD_ROWS ? (field * P.h + P.desth) / P.desth / 2 : 0;
-        sy = (y * P.h) / P.desth + field_offset;
+        const int field_offset = S::FIELD_ROWS ? (field * h + P.desth) / P.desth / 2 : 0;
+        sy = (y * h) / P.desth + field_offset;
     }
-    if (sy >= P.h) sy = (P.flags & CRTHIP_F_IMAGE_SPARE_ROW) ? P.h : P.h - 1;
+    if (sy >= h) sy = (P.flags & CRTHIP_F_IMAGE_SPARE_ROW) ? h : h - 1;
     if (sy < 0) sy = 0;
     return sy;
+}
+template <class S> __device__ __forceinline__ int source_row(const crthip_params &P, int y, int field)
+{
+    return source_row<S>(P, P.h, y, field);
 }
 
 /* FAST: 24-bit multiplies (always in range for the IIRs and the carrier products: 8-bit pixels
@@ -448,7 +453,13 @@ template <class S> __device__ __forceinline__ int source_row(const crthip_params
  * belong to two fields: nothing below takes either value for wave-uniform */
 /* HU: the carriers are the ones of the lane's field (crthip_hue_rec, crt_dev.h): the eight loads below go to the record where the
  * uniform instantiations read the blob (scalar loads there, per-lane ones here: crow was per lane already, now f is too) */
-template <class S, bool NOISE, bool FAST, bool IN4, bool CLAMP, int ACT, int OT = 16, int OL = OT, bool KN = false, bool LV = false, bool HU = false>
+/* SZ: w, h, col_step and the image's place are the ones of the WAVE's field (crthip_size_rec, crt_dev.h).  The grid gives every field
+ * whole wavefronts -- ceil(desth / 64) work items per field, the lanes beyond desth idle (NTSC: 20 of 256) -- so the field, and with it
+ * everything the sample loop takes for wave-uniform (w, the source column, have_col, the tile index), still IS wave-uniform: the
+ * record comes in by scalar loads, the loop is the uniform instantiation's plus one scalar min per sample (the column clamped to
+ * the record's own w - 1).  `istride` carries the extent of the image buffer (size_rec_checked).  block_item deals out the work
+ * items as it does for every other instantiation: an item is (field, group of 64 rows) instead of 64 rows of n * desth. */
+template <class S, bool NOISE, bool FAST, bool IN4, bool CLAMP, int ACT, int OT = 16, int OL = OT, bool KN = false, bool LV = false, bool HU = false, bool SZ = false>
 __global__ void __launch_bounds__(64)
 k_active(const crthip_params P, int n_fields, const unsigned char *__restrict__ images, size_t istride,
          signed char *__restrict__ dst, size_t fstride, const crthip_state *__restrict__ state,
@@ -462,27 +473,45 @@ k_active(const crthip_params P, int n_fields, const unsigned char *__restrict__ 
     __shared__ unsigned s_out[T::TO::DWORDS];
 
     const int lane = threadIdx.x;
-    const int gid = block_item(blockIdx.x, order_k, order_per) * 64 + lane;     /* workgroup order: crt_dev.h */
+    const int item = block_item(blockIdx.x, order_k, order_per);                /* workgroup order: crt_dev.h */
+    const int gid = item * 64 + lane;
     const int rows = P.desth;
-    const bool live = gid < n_fields * rows;
-    const int f = live ? gid / rows : 0;
-    const int y = live ? gid - f * rows : 0;
+    bool live_;
+    int f_, y_row;
+    size_view sz = { P.w, P.h, 0ull, 0ull };
+    if constexpr (SZ) {
+        static_assert(!S::IS_NES && !KN && !LV && !HU, "sizes: RGB input, no knob records (crt_hip.h, OUT OF SCOPE)");
+        const int per_field = (rows + 63) >> 6;
+        const bool item_ok = item < n_fields * per_field;
+        f_ = item_ok ? item / per_field : 0;                                    /* wave-uniform */
+        const int yy = (item - f_ * per_field) * 64 + lane;
+        live_ = item_ok && yy < rows;
+        y_row = live_ ? yy : 0;
+        sz = size_rec_checked(size_blob_recs(P)[f_], P.in_bpp, (P.flags & CRTHIP_F_IMAGE_SPARE_ROW) != 0, IN4, (unsigned long long) istride);
+    } else {
+        live_ = gid < n_fields * rows;
+        f_ = live_ ? gid / rows : 0;
+        y_row = live_ ? gid - f_ * rows : 0;
+    }
+    const bool live = live_;
+    const int f = f_;
+    const int y = y_row;
     const crthip_state st = state[f];
     int noise = P.noise;
     if constexpr (KN) noise = knob_blob_recs(P)[f].noise;
-    const unsigned char *img = images + (size_t) f * istride;
+    const unsigned char *img = SZ ? images + sz.off : images + (size_t) f * istride;
     const int start = (y + P.yo) * S::HRES + P.xo;
     unsigned rn = 0;
     if (NOISE) rn = lcg_at(jump16, (unsigned) st.rn, start);
 
-    const int w = P.w, destw = P.destw;
+    const int w = sz.w, destw = P.destw;
     const int qstep = w / destw, rstep = w - qstep * destw;   /* column = floor(x*w/destw), incrementally */
     int col = 0, err = 0;                                     /* wave-uniform */
     const int ngroups = (destw + 3) >> 2;
     const int wrap_x0 = wrapn > 0 ? destw - wrapn : 0x7fffffff;   /* staged sample tile: first sample that runs over the line's end */
 
     /* per-row source / destination, published to the whole wave */
-    const int sy = source_row<S>(P, y, st.field & 1);
+    const int sy = source_row<S>(P, sz.h, y, st.field & 1);
     const int in_bpp = S::IS_NES ? 2 : P.in_bpp;
     const unsigned char *row = img + (size_t) sy * w * in_bpp;
     T tiles;
@@ -589,7 +618,7 @@ k_active(const crthip_params P, int n_fields, const unsigned char *__restrict__ 
         int fy = 0, fi = 0, fq = 0, have_col = -1;                 /* YIQ of source column have_col (wave-uniform) */
         /* source column on the scalar unit: one 64-bit add per sample (crthip_params.col_step), instead of the
          * incremental quotient / remainder pair (8 scalar instructions as compiled) */
-        const unsigned long long cstep = ((unsigned long long) P.col_step_hi << 32) | P.col_step_lo;
+        const unsigned long long cstep = SZ ? sz.cstep : ((unsigned long long) P.col_step_hi << 32) | P.col_step_lo;
         unsigned long long cpos = 0;
         for (int g = 0; g < ngroups; g++) {
 #pragma unroll
@@ -600,6 +629,9 @@ k_active(const crthip_params P, int n_fields, const unsigned char *__restrict__ 
                  * (piece_offset) -- one compare and branch per sample less */
                 if (IN4 || x < destw) {
                     if constexpr (!S::IS_NES) col = (int) (cpos >> 32);
+                    /* sizes: the column never leaves the record's own row, on EITHER side, whatever col_step a rewritten record holds
+                     * (crt_size_guard.h; a no-op for the records of crthip_sizes_prepare) */
+                    if constexpr (SZ) col = size_col_clamped(col, w);
                     /* an upscaled line (w < destw) samples some source pixels twice: all 64 lanes are at the same
                      * column, so "same pixel as before" is a scalar branch that skips the fetch and the conversion */
                     if (col != have_col) {
@@ -1303,10 +1335,17 @@ static bool encoder_fast_ok(const crthip_ctx *c, const crthip_params *p)
     return ok;
 }
 
+template <class S, bool FAST>
+static void launch_active_sizes(crthip_ctx *c, const crthip_params *p, int n, const void *d_images,
+                                signed char *dst, const crthip_state *d_state, const sig_layout &lay);
+
 template <class S, bool FULL, bool FAST>
 static void launch_active(crthip_ctx *c, const crthip_params *p, int n, const void *d_images, size_t istride,
                           signed char *dst, const crthip_state *d_state, const sig_layout &lay)
 {
+    if constexpr (FULL && !S::IS_NES) {
+        if (c->size_recs) { launch_active_sizes<S, FAST>(c, p, n, d_images, dst, d_state, lay); return; }
+    }
     const int wrapn = lay.pitch != S::HRES ? lay.wrap : 0;      /* flat lines: a row that runs over its line's end simply continues */
     ProfScope ps(c, CRTHIP_K_ACTIVE);
     const int total = n * p->desth;
@@ -1439,6 +1478,49 @@ static void launch_active(crthip_ctx *c, const crthip_params *p, int n, const vo
     if (noise) { if (in4) CRTHIP_LAUNCH_ACTIVE(true, true); else CRTHIP_LAUNCH_ACTIVE(true, false); }
     else       { if (in4) CRTHIP_LAUNCH_ACTIVE(false, true); else CRTHIP_LAUNCH_ACTIVE(false, false); }
 #undef CRTHIP_LAUNCH_ACTIVE
+}
+
+/* A sizes call (crthip_fieldpass_sizes / crthip_stills_sizes; c->size_recs): k_active's SZ instantiations, always -- the lane-per-row
+ * shape whatever crthip_set_shape says (crt_hip.h).  The grid gives every field ceil(desth / 64) whole wavefronts; what the uniform
+ * launch decides by p->w is decided by the env's bounds, in ONE launch: the cooperative tiles need every row to hold a 16-byte piece
+ * (w_min >= 4), the wide image tile pays where every image fills whole 128-byte lines (w_min >= 1280; CRTHIP_AC_TILE and
+ * crthip_set_pixel_tile's encoder half override it as they do for the uniform launch).  The signal-tile rule is the uniform launch's, on
+ * this launch's own wave count.  Every choice gives identical bytes (tests/test_gpu_sizes.py runs them against each other). */
+template <class S, bool FAST>
+static void launch_active_sizes(crthip_ctx *c, const crthip_params *p, int n, const void *d_images,
+                                signed char *dst, const crthip_state *d_state, const sig_layout &lay)
+{
+    const int wrapn = lay.pitch != S::HRES ? lay.wrap : 0;
+    ProfScope ps(c, CRTHIP_K_ACTIVE);
+    const unsigned char *img = (const unsigned char *) d_images;
+    const size_t extent = ((size_t) c->size_env.extent_hi << 32) | c->size_env.extent_lo;
+    const int items = n * ((p->desth + 63) / 64);
+    const dim3 block(64);
+    const bool noise = p->noise != 0;
+    const bool in4 = p->in_bpp == 4 && c->size_env.w_min >= 4;
+    const block_order bo = make_block_order(items, c->act_order_env == -1 ? n : c->act_order_env);
+    const dim3 ogrid(bo.grid);
+    const bool wide_in = c->ac_tile_env ? c->ac_tile_env == 32 : c->ac_tile ? c->ac_tile == 32 : c->size_env.w_min >= 1280;
+#define CRTHIP_LAUNCH_ACTIVE_SZ(NZ, FA, I4, AC, OTV, OLV) \
+    hipLaunchKernelGGL((k_active<S, NZ, FA, I4, true, AC, OTV, OLV, false, false, false, true>), ogrid, block, 0, c->stream, *p, n, img, extent, dst, lay.fstride, d_state, c->d_jump16, bo.K, bo.per, lay.pitch, lay.shift, wrapn)
+    if constexpr (FAST && S::CCS == 4) {
+        const unsigned nw = (unsigned) items;
+        const bool big = c->sig_tile_env ? c->sig_tile_env != 16
+                       : wide_in ? nw >= (unsigned) SIG_TILE64_MIN_WAVES_WIDE
+                       : (nw > (unsigned) SIG_TILE32_BAND_LO && nw <= (unsigned) SIG_TILE32_ONE_ROUND) || nw > (unsigned) SIG_TILE16_ONE_ROUND;
+        if (in4 && big) {
+            if (wide_in) { if (noise) CRTHIP_LAUNCH_ACTIVE_SZ(true, true, true, 32, 64, CRTHIP_ENC_OL64); else CRTHIP_LAUNCH_ACTIVE_SZ(false, true, true, 32, 64, CRTHIP_ENC_OL64); }
+            else         { if (noise) CRTHIP_LAUNCH_ACTIVE_SZ(true, true, true, 16, 32, CRTHIP_ENC_OL32); else CRTHIP_LAUNCH_ACTIVE_SZ(false, true, true, 16, 32, CRTHIP_ENC_OL32); }
+            return;
+        }
+    }
+    if (in4) {
+        if (wide_in) { if (noise) CRTHIP_LAUNCH_ACTIVE_SZ(true, FAST, true, 32, 16, 16); else CRTHIP_LAUNCH_ACTIVE_SZ(false, FAST, true, 32, 16, 16); }
+        else         { if (noise) CRTHIP_LAUNCH_ACTIVE_SZ(true, FAST, true, 16, 16, 16); else CRTHIP_LAUNCH_ACTIVE_SZ(false, FAST, true, 16, 16, 16); }
+    } else {                                                     /* (bytewise pixels: the image tile is not used, one width of it serves) */
+        if (noise) CRTHIP_LAUNCH_ACTIVE_SZ(true, FAST, false, 16, 16, 16); else CRTHIP_LAUNCH_ACTIVE_SZ(false, FAST, false, 16, 16, 16);
+    }
+#undef CRTHIP_LAUNCH_ACTIVE_SZ
 }
 
 /* fused path: skeleton + noise for everything outside the active rectangle */

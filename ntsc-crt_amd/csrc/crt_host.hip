@@ -983,6 +983,12 @@ static int fieldpass_chunk(crthip_ctx *c, const crthip_params *p, int enc, int f
         if (level_call(c)) level_blob_set(&pk, level_blob_get(p) + first);
         if (hue_call(c)) hue_blob_set(&pk, hue_blob_get(p) + first);
         p = &pk;
+    } else if (c->size_recs) {
+        /* mixed sizes: likewise the size record of the chunk's first field; the images have no stride (istride == 0: img stays the
+         * base the records' offsets count from) */
+        pk = *p;
+        size_blob_set(&pk, c->size_recs + first);
+        p = &pk;
     }
     if (part & 1) {
         const bool vhs_rand = c->system == CRTHIP_SYSTEM_NTSCVHS && !(p->flags & CRTHIP_F_VHS_LCG_NOISE);
@@ -1121,7 +1127,7 @@ static int fieldpass_body(crthip_ctx *c, const crthip_params *p, int n, const vo
 int crthip_fieldpass(crthip_ctx *c, const crthip_params *p, int n, const void *d_images, size_t istride,
                      void *d_out, size_t ostride, crthip_state *d_state)
 {
-    if (c) c->knob_recs = nullptr;
+    if (c) { c->knob_recs = nullptr; c->size_recs = nullptr; }
     return fieldpass_body(c, p, n, d_images, istride, d_out, ostride, d_state);
 }
 
@@ -1202,8 +1208,53 @@ int crthip_fieldpass_knobs(crthip_ctx *c, const crthip_params *p, int n, const v
     rc = knobs_blob(c, p, n, d_recs, env, &q);
     if (rc) return rc;
     c->knob_recs = d_recs;
+    c->size_recs = nullptr;
     rc = fieldpass_body(c, &q, n, d_images, istride, d_out, ostride, d_state);
     c->knob_recs = nullptr;
+    return rc;
+}
+
+/* What both sizes entry points check (p went through check_params), and *q = the blob their launches carry: the device pointer to
+ * the size record of the call's field 0 in `reserved` (size_blob_set; fieldpass_chunk moves it to its chunk's first field).  The
+ * caller sets c->size_recs for the duration of its launches and clears it on every way out; c->size_env = the bounds the encoder's
+ * launch code decides by where the uniform call reads p->w.  The host sees the env, not the records: what it checks here is that the
+ * image a wavefront falls back to for a record it refuses (size_rec_checked, crt_dev.h) lies inside the extent. */
+static int sizes_blob(crthip_ctx *c, const crthip_params *p, int n, const void *d_images, const crthip_size_rec *d_srecs,
+                      const crthip_sizes_env *senv, crthip_params *q)
+{
+    if (!d_srecs || !senv) return set_err(c, CRTHIP_E_ARG, "sizes: no records / no env", hipSuccess);
+    if (CHECK_WORD(c, d_srecs)) return CRTHIP_E_ARG;
+    if (senv->magic != CRTHIP_SIZES_MAGIC) return set_err(c, CRTHIP_E_ARG, "sizes: env does not come from crthip_sizes_prepare", hipSuccess);
+    if (senv->n != n) return set_err(c, CRTHIP_E_ARG, "sizes: env was prepared for another number of fields", hipSuccess);
+    if (p->raw != 0) return set_err(c, CRTHIP_E_ARG, "sizes: raw images (the signal rectangle then depends on w and h)", hipSuccess);
+    if (c->system == CRTHIP_SYSTEM_NES) return set_err(c, CRTHIP_E_ARG, "sizes: the NES encoder (PPU pixels) has no per-field instantiation", hipSuccess);
+    if (p->in_bpp == 0) return set_err(c, CRTHIP_E_ARG, "sizes: an input format crt_modulate refuses", hipSuccess);
+    const size_t extent = ((size_t) senv->extent_hi << 32) | senv->extent_lo;
+    const bool spare = (p->flags & CRTHIP_F_IMAGE_SPARE_ROW) != 0;
+    const bool tiles = p->in_bpp == 4 && senv->w_min >= 4;
+    if (senv->w_min < 1 || senv->w_min > senv->w_max || senv->h_min < 1 || senv->h_min > senv->h_max ||
+        extent < (size_t) (tiles ? 4 : 1) * (size_t) p->in_bpp * (spare ? 2 : 1))
+        return set_err(c, CRTHIP_E_ARG, "sizes: the env's bounds contradict each other (not from crthip_sizes_prepare)", hipSuccess);
+    if (d_images && p->in_bpp == 4 && off_grid(d_images, 0, 4))
+        return set_err(c, CRTHIP_E_ARG, "d_images: 4-byte pixels need 4-byte alignment", hipSuccess);
+    *q = *p;
+    size_blob_set(q, d_srecs);
+    c->size_env = *senv;
+    return CRTHIP_OK;
+}
+
+int crthip_fieldpass_sizes(crthip_ctx *c, const crthip_params *p, int n, const void *d_images, void *d_out, size_t ostride,
+                           crthip_state *d_state, const crthip_size_rec *d_srecs, const crthip_sizes_env *senv)
+{
+    int rc = check_params(c, p, n);
+    if (rc) return rc;
+    crthip_params q;
+    rc = sizes_blob(c, p, n, d_images, d_srecs, senv, &q);
+    if (rc) return rc;
+    c->knob_recs = nullptr;
+    c->size_recs = d_srecs;
+    rc = fieldpass_body(c, &q, n, d_images, 0, d_out, ostride, d_state);
+    c->size_recs = nullptr;
     return rc;
 }
 
@@ -1346,7 +1397,7 @@ static int stills_body(crthip_ctx *c, const crthip_params *p, int n, const void 
 int crthip_stills(crthip_ctx *c, const crthip_params *p, int n, const void *d_images, size_t istride,
                   void *d_out, size_t ostride, crthip_state *d_state, int n_passes, const crthip_pass *sched)
 {
-    if (c) c->knob_recs = nullptr;
+    if (c) { c->knob_recs = nullptr; c->size_recs = nullptr; }
     return stills_body(c, p, n, d_images, istride, d_out, ostride, d_state, n_passes, sched);
 }
 
@@ -1363,8 +1414,27 @@ int crthip_stills_knobs(crthip_ctx *c, const crthip_params *p, int n, const void
     rc = knobs_blob(c, p, n, d_recs, env, &q);
     if (rc) return rc;
     c->knob_recs = d_recs;
+    c->size_recs = nullptr;
     rc = stills_body(c, &q, n, d_images, istride, d_out, ostride, d_state, n_passes, sched);
     c->knob_recs = nullptr;
+    return rc;
+}
+
+/* record k is still k's size in every pass; at noise 0 every distinct entry is encoded once with the records' blob (a still's clean
+ * signal depends on its own size, not on the pass) */
+int crthip_stills_sizes(crthip_ctx *c, const crthip_params *p, int n, const void *d_images, void *d_out, size_t ostride,
+                        crthip_state *d_state, int n_passes, const crthip_pass *sched,
+                        const crthip_size_rec *d_srecs, const crthip_sizes_env *senv)
+{
+    int rc = check_params(c, p, n);
+    if (rc) return rc;
+    crthip_params q;
+    rc = sizes_blob(c, p, n, d_images, d_srecs, senv, &q);
+    if (rc) return rc;
+    c->knob_recs = nullptr;
+    c->size_recs = d_srecs;
+    rc = stills_body(c, &q, n, d_images, 0, d_out, ostride, d_state, n_passes, sched);
+    c->size_recs = nullptr;
     return rc;
 }
 

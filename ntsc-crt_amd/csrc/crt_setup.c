@@ -418,6 +418,28 @@ rgb_carriers(const struct crt_sysdef *d, int chroma_pattern, int as_color, int h
     }
 }
 
+/* ceil(2^32 * w / destw) by long division (C89: no 64-bit type): crthip_params.col_step_lo / _hi, and crthip_size_rec's per field */
+static void
+col_step_for(int w, int destw, unsigned *step_lo, unsigned *step_hi)
+{
+    unsigned dw = (unsigned) (destw > 0 ? destw : 1), r = (unsigned) w % dw, lo = 0;
+    int i;
+
+    *step_hi = (unsigned) w / dw;
+    for (i = 0; i < 32; i++) {
+        r <<= 1;
+        lo <<= 1;
+        if (r >= dw) {
+            r -= dw;
+            lo |= 1u;
+        }
+    }
+    if (r != 0 && ++lo == 0) {
+        (*step_hi)++;
+    }
+    *step_lo = lo;
+}
+
 int
 crthip_params_finalize(crthip_params *p)
 {
@@ -561,23 +583,7 @@ crthip_params_finalize(crthip_params *p)
     p->ire_base = d.black_level + p->black_point;
     p->dx = ((d.av_len - 1) << 12) / p->outw;
     p->ratio = (((p->outh << 16) / d.lines) + 32768) >> 16;
-    {   /* ceil(2^32 * w / destw) by long division (C89: no 64-bit type) */
-        unsigned dw = (unsigned) (p->destw > 0 ? p->destw : 1), r = (unsigned) p->w % dw, lo = 0;
-        int i;
-        p->col_step_hi = (unsigned) p->w / dw;
-        for (i = 0; i < 32; i++) {
-            r <<= 1;
-            lo <<= 1;
-            if (r >= dw) {
-                r -= dw;
-                lo |= 1u;
-            }
-        }
-        if (r != 0 && ++lo == 0) {
-            p->col_step_hi++;
-        }
-        p->col_step_lo = lo;
-    }
+    col_step_for(p->w, p->destw, &p->col_step_lo, &p->col_step_hi);
     p->bloom_max_e = (128 + (p->noise / 2)) * d.av_len;         /* crt_core.c:400 */
     if (p->bloom && (p->bloom_max_e <= 0 || p->noise < 0)) {
         /* max_e <= 0: the reference divides by zero (:522).  noise < 0 shrinks max_e, the beam-energy term then drives
@@ -883,6 +889,100 @@ crthip_knobs_prepare8(const crthip_params *p, int n, const crthip_knobs8 *knobs,
     memset(henv, 0, sizeof(*henv));
     henv->magic = CRTHIP_HUES_MAGIC;
     henv->n = n;
+    return CRTHIP_OK;
+}
+
+/* ------------------------------------------------------------------------- */
+/* mixed image sizes (crthip_fieldpass_sizes, crthip_stills_sizes)             */
+/* ------------------------------------------------------------------------- */
+/*
+ * The per-field size records and their bounds.  Field by field a copy of p with the field's w and h goes through
+ * crthip_params_finalize -- its refusals are this call's, its col_step the record's -- and must leave the signal geometry and
+ * the layout verdict of p itself where they are: that is what lets ONE launch sequence serve every size.  Offsets and the extent
+ * are byte counts in size_t (the ABI's own 64-bit type; the records carry them as two words).
+ */
+int
+crthip_sizes_prepare(const crthip_params *p, int n, const crthip_size *sizes, crthip_size_rec *recs, crthip_sizes_env *env)
+{
+    struct crt_sysdef d;
+    int k, shape, lay0[3][4], verdict0[3];
+    size_t fs0[3], extent = 0;
+    const size_t size_max = ~(size_t) 0;
+
+    if (p == 0 || sizes == 0 || recs == 0 || env == 0 || n <= 0 || p->finalized != CRTHIP_PARAMS_MAGIC ||
+        crt_sysdef_get(&d, p->system, p->chroma_pattern) != CRTHIP_OK) {
+        return CRTHIP_E_ARG;
+    }
+    if (p->raw != 0 || d.ppu_input || p->in_bpp == 0) {
+        return CRTHIP_E_ARG;
+    }
+    for (shape = 0; shape <= 2; shape++) {
+        verdict0[shape] = crthip_signal_layout_query(p, n, shape, lay0[shape], &fs0[shape]);
+        if (verdict0[shape] < 0) {
+            return CRTHIP_E_ARG;
+        }
+    }
+    memset(env, 0, sizeof(*env));
+    for (k = 0; k < n; k++) {
+        crthip_params q = *p;
+        const size_t off = ((size_t) sizes[k].off_hi << 16 << 16) | (size_t) sizes[k].off_lo;
+        size_t rows, row_bytes, bytes;
+        int lay[4];
+        size_t fs;
+
+        q.w = sizes[k].w;
+        q.h = sizes[k].h;
+        if (crthip_params_finalize(&q) != CRTHIP_OK) {
+            return CRTHIP_E_ARG;
+        }
+        if (q.destw != p->destw || q.desth != p->desth || q.xo != p->xo || q.yo != p->yo || q.in_bpp != p->in_bpp) {
+            return CRTHIP_E_ARG;
+        }
+        for (shape = 0; shape <= 2; shape++) {
+            if (crthip_signal_layout_query(&q, n, shape, lay, &fs) != verdict0[shape] || fs != fs0[shape] ||
+                memcmp(lay, lay0[shape], sizeof(lay)) != 0) {
+                return CRTHIP_E_ARG;
+            }
+        }
+        if (p->in_bpp == 4 && (off & 3) != 0) {
+            return CRTHIP_E_ARG;
+        }
+        rows = (size_t) q.h + ((p->flags & CRTHIP_F_IMAGE_SPARE_ROW) ? 1 : 0);
+        row_bytes = (size_t) q.w * (size_t) p->in_bpp;
+        if (row_bytes > size_max / rows) {
+            return CRTHIP_E_ARG;
+        }
+        bytes = rows * row_bytes;
+        if (bytes > size_max - off) {
+            return CRTHIP_E_ARG;
+        }
+        memset(&recs[k], 0, sizeof(recs[k]));
+        recs[k].w = q.w;
+        recs[k].h = q.h;
+        recs[k].col_step_lo = q.col_step_lo;
+        recs[k].col_step_hi = q.col_step_hi;
+        recs[k].off_lo = sizes[k].off_lo;
+        recs[k].off_hi = sizes[k].off_hi;
+        if (k == 0 || q.w < env->w_min) {
+            env->w_min = q.w;
+        }
+        if (k == 0 || q.w > env->w_max) {
+            env->w_max = q.w;
+        }
+        if (k == 0 || q.h < env->h_min) {
+            env->h_min = q.h;
+        }
+        if (k == 0 || q.h > env->h_max) {
+            env->h_max = q.h;
+        }
+        if (off + bytes > extent) {
+            extent = off + bytes;
+        }
+    }
+    env->magic = CRTHIP_SIZES_MAGIC;
+    env->n = n;
+    env->extent_lo = (unsigned) (extent & 0xffffffffu);
+    env->extent_hi = (unsigned) (extent >> 16 >> 16);
     return CRTHIP_OK;
 }
 

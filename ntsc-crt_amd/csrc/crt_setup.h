@@ -66,6 +66,7 @@ void crt_setup_vhs_power_table(unsigned long first, unsigned long step, int coun
 #define CRTHIP_KNOBS_MAGIC  0x43524b31            /* "CRK1": crthip_knobs_env of crthip_knobs_prepare */
 #define CRTHIP_LEVELS_MAGIC 0x43524c31            /* "CRL1": crthip_levels_env of crthip_knobs_prepare7 */
 #define CRTHIP_HUES_MAGIC   0x43524831            /* "CRH1": crthip_hues_env of crthip_knobs_prepare8 */
+#define CRTHIP_SIZES_MAGIC  0x43525a31            /* "CRZ1": crthip_sizes_env of crthip_sizes_prepare */
 #define CRTHIP_HUE_ABS_MAX  200000                /* a per-field encoder hue beyond it is refused: (angle + hue) * 8192 is computed in ints */
 
 /* CRTHIP_F_PHOSPHOR_FADE / _CLEAR (crt_hip.h): fade^CRTHIP_PHOSPHOR_DEPTH(c) == 0 for every byte c, fade^(DEPTH-1)(255) != 0 */

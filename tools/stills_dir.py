@@ -1,12 +1,16 @@
 #!/usr/bin/env python3
 """Finished stills for a folder of images: what the reference's `ntsc` program (crt_main.c) writes for every file, in batches.
 
-    python tools/stills_dir.py [-m|f|p|r] OUTW OUTH NOISE HUE IN_DIR OUT_DIR
+    python tools/stills_dir.py [--one-call] [-m|f|p|r] OUTW OUTH NOISE HUE IN_DIR OUT_DIR
 
 The flags are `ntsc`'s (crt_main.c:95-110): m monochrome, f start at the odd field, p progressive, r raw (no scaling); o is accepted
 and ignored (existing files are overwritten), a (analog dumps) is not available.  Every P6 .ppm of IN_DIR is read; files of equal
 size form a batch (the parameters are uniform per batch) that goes through ONE crthip_stills call (CRT.stills: at noise 0 every
 distinct field / frame of the schedule is encoded once for the batch); OUT_DIR/<name>.ppm is byte-identical to `ntsc`'s output.
+
+--one-call: the files are NOT grouped by size; the whole folder (MAX_BATCH files at a time) goes through one crthip_stills_sizes call
+(CRT.stills_sizes: every still with its own w and h), with byte-identical output files.  Not with r: raw images are refused there
+(the signal rectangle then depends on the image size).  The default stays the grouped path.
 
 PPM reading and writing are numpy: ppm_read24 / ppm_write24 (ppm_rw.c) restated.  The pixels travel as RGB24 in both directions
 (CRTHIP_FMT_RGB): the encoder reads the same r, g, b whatever the byte order, and the colour bytes of the decoder's blended BGRA
@@ -93,8 +97,24 @@ def convert_batch(crtlib, torch, imgs, outw, outh, noise, hue, opt):
     return out
 
 
+def convert_mixed(crtlib, torch, imgs, outw, outh, noise, hue, opt):
+    """imgs: a list of n [h_k, w_k, 3] uint8 RGB images of any sizes -> [n, outh, outw, 3] uint8 RGB, in ONE stills_sizes call"""
+    crt = crtlib.CRT(len(imgs), outw, outh, crtlib.FMT_RGB, "ntsc", device=0)
+    crt.blend = crt.scanlines = 1                                   # crt_main.c:235-236
+    s = crtlib.Settings(None, format=crtlib.FMT_RGB, raw=0, as_color=opt["docolor"], hue=hue, spare_row=False)
+    data = [torch.from_numpy(np.array(px)).to(crt.dev) for px in imgs]        # (a copy: read_ppm's arrays are read-only views)
+    crt.stills_sizes(data, noise, interlaced=not opt["progressive"], first_field=opt["field"], frames=4, settings=s)
+    crt.synchronize()
+    out = crt.out.cpu().numpy()
+    crt.close()
+    return out
+
+
 def main(argv):
     args = argv[1:]
+    one_call = "--one-call" in args
+    if one_call:
+        args.remove("--one-call")
     opt = parse_flags(args.pop(0)) if args and args[0].startswith("-") else parse_flags("")
     if len(args) != 6:
         raise SystemExit(__doc__)
@@ -105,12 +125,25 @@ def main(argv):
     import torch
     import crtlib
     names = sorted(f for f in os.listdir(in_dir) if f.lower().endswith(".ppm"))
+    if one_call and opt["raw"]:
+        raise SystemExit("--one-call: raw images (r) keep the grouped path")
     by_size = {}
     for name in names:
         px = read_ppm(os.path.join(in_dir, name))
         by_size.setdefault(px.shape[:2], []).append((name, px))
     os.makedirs(out_dir, exist_ok=True)
     done = 0
+    if one_call:
+        files = [(name, px) for _, group in sorted(by_size.items()) for name, px in group]
+        for lo in range(0, len(files), MAX_BATCH):
+            part = files[lo:lo + MAX_BATCH]
+            out = convert_mixed(crtlib, torch, [px for _, px in part], outw, outh, noise, hue, opt)
+            for (name, _), pic in zip(part, out):
+                write_ppm(os.path.join(out_dir, os.path.splitext(name)[0] + ".ppm"), pic)
+            done += len(part)
+            print("mixed sizes: %d stills in one call" % len(part))
+        print("done: %d files" % done)
+        return 0
     for (h, w), files in sorted(by_size.items()):
         for lo in range(0, len(files), MAX_BATCH):
             part = files[lo:lo + MAX_BATCH]
