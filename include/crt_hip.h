@@ -399,7 +399,8 @@ int  crthip_fieldpass(crthip_ctx *ctx, const crthip_params *p, int n,
  * not match; d_hues off its 4-byte alignment; CRTHIP_SYSTEM_PV1K (as for every knob); CRTHIP_SYSTEM_NES, whose PPU encoder has no
  * per-field instantiation (as for the levels).
  * OUT OF SCOPE: as_color and raw per field (keys SPACE and t), NES and PV-1000, knob videos through shard.py / crt_hip_node.h.
- * (Finished stills with one look per still: crthip_stills_knobs, under STILLS below.)
+ * (Finished stills with one look per still: crthip_stills_knobs, under STILLS below.  Knob records for a batch of MIXED image sizes:
+ * crthip_fieldpass_sizes_knobs / crthip_stills_sizes_knobs, under MIXED IMAGE SIZES below.)
  */
 typedef struct crthip_knobs     { int noise, mon_hue, saturation, reserved; } crthip_knobs;                                /* 16 bytes */
 typedef struct crthip_knobs5    { int noise, mon_hue, saturation, brightness, contrast, reserved[3]; } crthip_knobs5;      /* 32 bytes */
@@ -643,8 +644,32 @@ int  crthip_stills_knobs(crthip_ctx *ctx, const crthip_params *p, int n,
  * depends on ITS size, not on the pass), into the same workspace (crthip_stills_reserve).  Accepted and refused: what crthip_stills
  * and crthip_fieldpass_sizes accept and refuse.  crthip_fieldpass_signal after the call is refused, as after crthip_stills.
  * Nothing of either call survives it: every other entry point launches exactly the kernels it launched before.
- * OUT OF SCOPE: sizes combined with knob records (crthip_fieldpass_knobs and its siblings keep one size per batch), NES,
- * raw images, sequence mode, shard.py / crt_hip_node.h (a video has one size).
+ *
+ * SIZES WITH KNOB RECORDS -- a folder of photos of mixed sizes in which every photo gets its own look, a contact sheet of one picture
+ * per file under per-file settings.
+ * crthip_fieldpass_sizes_knobs: bit for bit and state for state what n calls of crthip_fieldpass with n = 1 give, call k made with
+ * field k's w, h and image (as crthip_fieldpass_sizes) AND field k's noise, monitor hue, saturation, brightness, contrast, black point,
+ * white point and encoder hue (as crthip_fieldpass_knobs).  d_srecs / senv: exactly as for crthip_fieldpass_sizes; d_recs / env: exactly
+ * as for crthip_fieldpass_knobs -- the records of crthip_sizes_prepare and of crthip_knobs_prepare / 5 / 7 / 8 as they are, no further
+ * prepare function; level records (crthip_bind_levels) and hue records (crthip_bind_hues) are read while bound and require lenv->n ==
+ * n / henv->n == n.  Record k of each array belongs to field k.
+ * crthip_stills_sizes_knobs: what n_passes calls of crthip_fieldpass_sizes_knobs give, d_state[k].field / .frame / .aux set to
+ * sched[r] before call r.  It shares its body with crthip_stills; the clean signal is shared when env->noise_max == 0, encoded once
+ * per distinct entry with every still's own size, levels and hue.  crthip_fieldpass_signal after it is refused.
+ *   Accepted: what BOTH parents accept -- every 4-sample RGB-input system, both VHS noise models, bloom, FIR, the phosphor flags,
+ *   blend, all six input formats, both signal layouts, overlap chunks, graph capture after crthip_reserve / crthip_stills_reserve
+ *   (records rewritten between replays stay inside the captured senv / env / lenv / henv).
+ *   Refused before anything is launched (CRTHIP_E_ARG, crthip_error_string says why; d_out and d_state untouched): what EITHER parent
+ *   refuses -- CRTHIP_SYSTEM_NES, CRTHIP_SYSTEM_PV1K, p->raw != 0, an input format crt_modulate refuses, a senv / env / lenv / henv
+ *   whose magic or n does not match or whose words contradict each other, records off their 4-byte alignment, d_images off its
+ *   alignment for the 4-byte formats, both phosphor flags at once, with levels bound CRTHIP_F_NES_BORDER.
+ *   Encoder: lane-per-scanline as for every sizes call -- k_active's SZ instantiations with KN (env->noise_max != 0), LV (levels
+ *   bound) and HU (hues bound).  In a sizes grid the field is wave-uniform: the noise gain, white, ire_base and the base of the hue
+ *   record are scalar loads there, where crthip_fieldpass_knobs loads them per lane.  These instantiations exist for the 64-byte
+ *   signal pieces (bytewise, narrow and wide image tile); the large signal tiles are not taken by such a call.  Identical bytes.
+ *   ADDRESS SAFETY is that of crthip_fieldpass_sizes, unchanged: the size is still the only thing that enters an address.
+ * Nothing of either call survives it (the context's knob, size, level and hue call marks are cleared on every way out).
+ * OUT OF SCOPE: NES, raw images, sequence mode, shard.py / crt_hip_node.h (a video has one size).
  */
 typedef struct crthip_size      { int w, h; unsigned off_lo, off_hi; } crthip_size;                                          /* 16 bytes */
 typedef struct crthip_size_rec  { int w, h; unsigned col_step_lo, col_step_hi, off_lo, off_hi; int reserved[2]; } crthip_size_rec;   /* 32 bytes */
@@ -658,6 +683,15 @@ int  crthip_stills_sizes(crthip_ctx *ctx, const crthip_params *p, int n, const v
                          void *d_out, size_t out_stride, crthip_state *d_state,
                          int n_passes, const crthip_pass *sched /* host */,
                          const crthip_size_rec *d_srecs /* n, DEVICE */, const crthip_sizes_env *senv /* host */);
+int  crthip_fieldpass_sizes_knobs(crthip_ctx *ctx, const crthip_params *p, int n, const void *d_images,
+                                  void *d_out, size_t out_stride, crthip_state *d_state,
+                                  const crthip_size_rec *d_srecs /* n, DEVICE */, const crthip_sizes_env *senv /* host */,
+                                  const crthip_knob_rec *d_recs /* n, DEVICE */, const crthip_knobs_env *env /* host */);
+int  crthip_stills_sizes_knobs(crthip_ctx *ctx, const crthip_params *p, int n, const void *d_images,
+                               void *d_out, size_t out_stride, crthip_state *d_state,
+                               int n_passes, const crthip_pass *sched /* host */,
+                               const crthip_size_rec *d_srecs /* n, DEVICE */, const crthip_sizes_env *senv /* host */,
+                               const crthip_knob_rec *d_recs /* n, DEVICE */, const crthip_knobs_env *env /* host */);
 
 /*
  * The phases of crthip_sequence, for hosts that cut ONE video over several contexts / devices / processes

@@ -301,6 +301,10 @@ def load_library():
         L.crthip_sizes_prepare.argtypes = [PP, ci, C.POINTER(Size), C.POINTER(SizeRec), C.POINTER(SizesEnv)]
         L.crthip_fieldpass_sizes.argtypes = [vp, PP, ci, vp, vp, sz, vp, vp, C.POINTER(SizesEnv)]
         L.crthip_stills_sizes.argtypes = [vp, PP, ci, vp, vp, sz, vp, ci, C.POINTER(Pass), vp, C.POINTER(SizesEnv)]
+    if hasattr(L, "crthip_fieldpass_sizes_knobs"):                # (likewise)
+        L.crthip_fieldpass_sizes_knobs.argtypes = [vp, PP, ci, vp, vp, sz, vp, vp, C.POINTER(SizesEnv), vp, C.POINTER(KnobsEnv)]
+        L.crthip_stills_sizes_knobs.argtypes = [vp, PP, ci, vp, vp, sz, vp, ci, C.POINTER(Pass), vp, C.POINTER(SizesEnv),
+                                                vp, C.POINTER(KnobsEnv)]
     _LIB = L
     return L
 
@@ -841,6 +845,61 @@ class CRT:
                                         C.c_void_p(self.out.data_ptr()), self.out.stride(0), C.c_void_p(self.state.data_ptr()),
                                         len(buf), buf, C.c_void_p(self.size_recs.data_ptr()), C.byref(self._size_env))
         self._check(rc, "crthip_stills_sizes")
+        s.initialized = 1
+
+    # ------------------------------------------------------------------ mixed image sizes, one look per field
+    def _sizes_knobs_upload(self, images, knobs, p, what):
+        """the uploads of fieldpass_sizes_knobs / stills_sizes_knobs: the counts are compared with each other and with this CRT's n
+        BEFORE anything reaches the library"""
+        if not hasattr(self.L, "crthip_fieldpass_sizes_knobs"):
+            raise RuntimeError("this libcrthip.so has no crthip_fieldpass_sizes_knobs")
+        n_img = None if images is None else int(len(images[1])) if isinstance(images, tuple) else len(images)
+        n_knob = None if knobs is None else int(knobs.shape[0]) if hasattr(knobs, "shape") else len(knobs)
+        if n_img is not None and n_knob is not None and n_img != n_knob:
+            raise ValueError("%s: %d images but %d looks" % (what, n_img, n_knob))
+        for cnt, noun in ((n_img, "images"), (n_knob, "looks")):
+            if cnt is not None and cnt != self.n:
+                raise ValueError("%s: %d %s for a batch of %d fields" % (what, cnt, noun, self.n))
+        if images is not None:
+            self.upload_sizes(images, p)
+        if knobs is not None:
+            self.upload_knobs(knobs, p)
+        if self.size_recs is None:
+            raise ValueError("%s(None, ...): no sizes uploaded yet (upload_sizes)" % what)
+        if self.knob_recs is None:
+            raise ValueError("%s(..., None): no knobs uploaded yet (upload_knobs)" % what)
+
+    def fieldpass_sizes_knobs(self, images, knobs, params=None, settings=None):
+        """fieldpass for a batch of MIXED image sizes in which every field has its own look (crthip_fieldpass_sizes_knobs):
+        ``images`` as for fieldpass_sizes -- a list of device tensors, a (buffer, (n, 3)) tuple, or None: the last upload_sizes --,
+        ``knobs`` as for fieldpass_knobs -- an (n, 3 | 5 | 7 | 8) integer array or tensor, or None: the last upload_knobs.  Row k of
+        both belongs to field k; a length mismatch raises ValueError before anything reaches the library.  ``settings`` /
+        ``params`` as for fieldpass_sizes; the blob's own noise, mon_hue, saturation (and what wider rows replace) are ignored."""
+        s = settings if settings is not None else Settings(None)
+        p = params if params is not None else self.sizes_params(s, 0)
+        self._sizes_knobs_upload(images, knobs, p, "fieldpass_sizes_knobs")
+        if params is None:
+            self._load_field_state(s)
+        rc = self.L.crthip_fieldpass_sizes_knobs(self.ctx, C.byref(p), self.n, C.c_void_p(self._size_buf.data_ptr()),
+                                                 C.c_void_p(self.out.data_ptr()), self.out.stride(0), C.c_void_p(self.state.data_ptr()),
+                                                 C.c_void_p(self.size_recs.data_ptr()), C.byref(self._size_env),
+                                                 C.c_void_p(self.knob_recs.data_ptr()), C.byref(self._knob_env))
+        self._check(rc, "crthip_fieldpass_sizes_knobs")
+        s.initialized = 1
+
+    def stills_sizes_knobs(self, images, knobs, interlaced=True, first_field=0, frames=4, schedule=None, params=None, settings=None):
+        """stills for images of MIXED sizes, each with its own look (crthip_stills_sizes_knobs): ``images`` / ``knobs`` /
+        ``settings`` / ``params`` as for fieldpass_sizes_knobs, the schedule as for stills().  With every still at noise 0 each
+        distinct schedule entry is encoded once, with every still's own size, levels and hue."""
+        buf = self._stills_passes(interlaced, first_field, frames, schedule)
+        s = settings if settings is not None else Settings(None)
+        p = params if params is not None else self.sizes_params(s, 0)
+        self._sizes_knobs_upload(images, knobs, p, "stills_sizes_knobs")
+        rc = self.L.crthip_stills_sizes_knobs(self.ctx, C.byref(p), self.n, C.c_void_p(self._size_buf.data_ptr()),
+                                              C.c_void_p(self.out.data_ptr()), self.out.stride(0), C.c_void_p(self.state.data_ptr()),
+                                              len(buf), buf, C.c_void_p(self.size_recs.data_ptr()), C.byref(self._size_env),
+                                              C.c_void_p(self.knob_recs.data_ptr()), C.byref(self._knob_env))
+        self._check(rc, "crthip_stills_sizes_knobs")
         s.initialized = 1
 
     def stills_reserve(self, n_distinct):

@@ -513,7 +513,35 @@ __device__ __forceinline__ const crthip_size_rec *size_blob_recs(const crthip_pa
 {
     return (const crthip_size_rec *) (((unsigned long long) (unsigned) P.reserved[1] << 32) | (unsigned) P.reserved[0]);
 }
-#include "crt_size_guard.h"     /* size_view, size_rec_checked, size_col_clamped: plain C++, also compiled for the host by tests/test_sizes_cpu.py */
+/* Sizes WITH knob records (crthip_fieldpass_sizes_knobs / crthip_stills_sizes_knobs): `reserved` is taken by the knob records, white /
+ * ire_base by the levels, burst[0][0..1] by the hues.  The size records' pointer of such a call lives in col_step_lo / _hi -- words a
+ * sizes call does not read as values (the SZ kernels take col_step from the record; crthip_params_finalize's check of them has passed
+ * on the caller's blob before the library's copy is made, and a device pointer is never the 0 check_encoder looks for).  The only
+ * readers are k_active's SZ instantiations with KN, LV or HU and the launch code in front of them (launch_active_sizes, which hands the
+ * plain SZ kernel a copy with the pointer back in `reserved`). */
+static_assert(offsetof(crthip_params, col_step_hi) == offsetof(crthip_params, col_step_lo) + sizeof(unsigned), "col_step_lo and _hi are neighbours: one device pointer");
+static inline void size_blob_knobs_set(crthip_params *q, const crthip_size_rec *d_srecs)
+{
+    static_assert(2 * sizeof(unsigned) == sizeof(d_srecs), "a device pointer fits crthip_params.col_step_lo + _hi");
+    memcpy(&q->col_step_lo, &d_srecs, sizeof(unsigned));
+    memcpy(&q->col_step_hi, (const char *) &d_srecs + sizeof(unsigned), sizeof(unsigned));
+}
+static inline const crthip_size_rec *size_blob_knobs_get(const crthip_params *q)
+{
+    return (const crthip_size_rec *) (((unsigned long long) q->col_step_hi << 32) | q->col_step_lo);
+}
+__device__ __forceinline__ const crthip_size_rec *size_blob_recs_knobs(const crthip_params &P)
+{
+    return (const crthip_size_rec *) (((unsigned long long) P.col_step_hi << 32) | P.col_step_lo);
+}
+/* One int of a record at a WAVE-UNIFORM address, by a scalar load: the record arrays are read only for the duration of a launch
+ * (crt_hip.h), so the load may go through the constant address space, where a uniform address gives s_load_dword and the value
+ * lives in a scalar register.  (A plain load through a pointer made from two blob words is a per-lane flat load, uniform or not.) */
+__device__ __forceinline__ int uniform_rec_int(const int *p)
+{
+    return *(const __attribute__((address_space(4))) int *) (unsigned long long) p;
+}
+#include "crt_size_guard.h"    /* size_view, size_rec_checked, size_col_clamped: plain C++, also compiled for the host by tests/test_sizes_cpu.py */
 
 /* Picture knobs (crthip_knobs_prepare5): is a call with such records under way?  The decoders then launch their PK instantiations */
 static inline bool knob_pic_call(const crthip_ctx *c);

@@ -459,6 +459,11 @@ template <class S> __device__ __forceinline__ int source_row(const crthip_params
  * record comes in by scalar loads, the loop is the uniform instantiation's plus one scalar min per sample (the column clamped to
  * the record's own w - 1).  `istride` carries the extent of the image buffer (size_rec_checked).  block_item deals out the work
  * items as it does for every other instantiation: an item is (field, group of 64 rows) instead of 64 rows of n * desth. */
+/* SZ with KN / LV / HU (crthip_fieldpass_sizes_knobs / crthip_stills_sizes_knobs): f is wave-uniform here, so the noise gain, white,
+ * ire_base and the base of the field's crthip_hue_rec come in by SCALAR loads like the size record and stay scalar -- the sample loop
+ * is the SZ loop with the uniform instantiation's scalar multipliers (mad24_vv), not the per-lane knob loop (mad24_vvv); only the
+ * carrier row crow, and with it the eight carrier loads, stays per lane.  The size records' pointer of such a launch lives in the
+ * blob's col_step words (size_blob_recs_knobs, crt_dev.h); the size is still the only thing that enters an address. */
 template <class S, bool NOISE, bool FAST, bool IN4, bool CLAMP, int ACT, int OT = 16, int OL = OT, bool KN = false, bool LV = false, bool HU = false, bool SZ = false>
 __global__ void __launch_bounds__(64)
 k_active(const crthip_params P, int n_fields, const unsigned char *__restrict__ images, size_t istride,
@@ -469,6 +474,8 @@ k_active(const crthip_params P, int n_fields, const unsigned char *__restrict__ 
      * (crt_dev.h, sig_layout; wrapn = the row's samples that run over the end of its line) */
     using T = RowTiles<ACT, OT, OL>;
     constexpr int AC_SHIFT = ACT == 32 ? 5 : 4;
+    /* the noise gain / white as VECTOR multipliers: where the lanes of a wave may belong to two fields, i.e. not in a sizes grid */
+    constexpr bool KNV = KN && !SZ, LVV = LV && !SZ;
     __shared__ unsigned s_pix[T::TP::DWORDS];
     __shared__ unsigned s_out[T::TO::DWORDS];
 
@@ -480,14 +487,16 @@ k_active(const crthip_params P, int n_fields, const unsigned char *__restrict__ 
     int f_, y_row;
     size_view sz = { P.w, P.h, 0ull, 0ull };
     if constexpr (SZ) {
-        static_assert(!S::IS_NES && !KN && !LV && !HU, "sizes: RGB input, no knob records (crt_hip.h, OUT OF SCOPE)");
+        static_assert(!S::IS_NES, "sizes: RGB input (crt_hip.h, OUT OF SCOPE)");
+        static_assert(!(KN || LV || HU) || S::CCS == 4, "sizes with knob records: the 4-sample systems (knobs_blob refuses the PV-1000)");
         const int per_field = (rows + 63) >> 6;
         const bool item_ok = item < n_fields * per_field;
         f_ = item_ok ? item / per_field : 0;                                    /* wave-uniform */
         const int yy = (item - f_ * per_field) * 64 + lane;
         live_ = item_ok && yy < rows;
         y_row = live_ ? yy : 0;
-        sz = size_rec_checked(size_blob_recs(P)[f_], P.in_bpp, (P.flags & CRTHIP_F_IMAGE_SPARE_ROW) != 0, IN4, (unsigned long long) istride);
+        const crthip_size_rec *srecs = (KN || LV || HU) ? size_blob_recs_knobs(P) : size_blob_recs(P);
+        sz = size_rec_checked(srecs[f_], P.in_bpp, (P.flags & CRTHIP_F_IMAGE_SPARE_ROW) != 0, IN4, (unsigned long long) istride);
     } else {
         live_ = gid < n_fields * rows;
         f_ = live_ ? gid / rows : 0;
@@ -498,7 +507,8 @@ k_active(const crthip_params P, int n_fields, const unsigned char *__restrict__ 
     const int y = y_row;
     const crthip_state st = state[f];
     int noise = P.noise;
-    if constexpr (KN) noise = knob_blob_recs(P)[f].noise;
+    if constexpr (KN && SZ) noise = uniform_rec_int(&knob_blob_recs(P)[f].noise);      /* f is wave-uniform: a scalar load */
+    else if constexpr (KN) noise = knob_blob_recs(P)[f].noise;
     const unsigned char *img = SZ ? images + sz.off : images + (size_t) f * istride;
     const int start = (y + P.yo) * S::HRES + P.xo;
     unsigned rn = 0;
@@ -571,7 +581,8 @@ k_active(const crthip_params P, int n_fields, const unsigned char *__restrict__ 
         }
         const int cy_ = P.iir_c[0], ci_ = P.iir_c[1], cq_ = P.iir_c[2];
         int white = P.white, ire_base = P.ire_base;
-        if constexpr (LV) { const crthip_level_rec lv = level_blob_recs(P)[f]; white = lv.white; ire_base = lv.ire_base; }
+        if constexpr (LV && SZ) { const crthip_level_rec *lv = level_blob_recs(P) + f; white = uniform_rec_int(&lv->white); ire_base = uniform_rec_int(&lv->ire_base); }
+        else if constexpr (LV) { const crthip_level_rec lv = level_blob_recs(P)[f]; white = lv.white; ire_base = lv.ire_base; }
         int hy = 0, hi = 0, hq = 0;
         const bool hipass = (P.flags & CRTHIP_F_HIPASS) != 0;
         int cph = 0;                                              /* x % CCS for the 5-sample system (wave-uniform) */
@@ -703,10 +714,10 @@ k_active(const crthip_params P, int n_fields, const unsigned char *__restrict__ 
                         const int nb = (int) ((rn >> 16) & 0xffu);
                         __builtin_amdgcn_sched_barrier(0);
                         const int pQ = __mul24(oq, ccQ);
-                        const int nz = KN ? mad24_vvv(nb, noise256, neg_noise127_256) : mad24_vv(nb, noise256, neg_noise127_256);
+                        const int nz = KNV ? mad24_vvv(nb, noise256, neg_noise127_256) : mad24_vv(nb, noise256, neg_noise127_256);
                         __builtin_amdgcn_sched_barrier(0);
                         const int miq = add_hiwords(pI, pQ);
-                        ire = LV ? mad24_vvv(oy + miq, white64, ire_base_65536) : mad24_vv(oy + miq, white64, ire_base_65536);
+                        ire = LVV ? mad24_vvv(oy + miq, white64, ire_base_65536) : mad24_vv(oy + miq, white64, ire_base_65536);
                         ire = clampi(ire, 0, (110 << 16) | 0xffff);
                         ire = add_hiwords(ire, nz);
                         ire = clampi(ire, -127, 127);
@@ -723,8 +734,8 @@ k_active(const crthip_params P, int n_fields, const unsigned char *__restrict__ 
                         /* (r6) with noise to add, the >> 10 is not taken at all: white and the base scaled by another 2^6 leave the
                          * level in the HIGH word, the clamp to [0, 110] works on the scaled value (monotone: same result), and the
                          * noise add below takes the high words of both its operands (|white| < 2^17, host-checked) */
-                        if (NOISE) ire = LV ? mad24_vvv(oy + miq, white64, ire_base_65536) : mad24_vv(oy + miq, white64, ire_base_65536);
-                        else ire = (LV ? mad24_vvv(oy + miq, white, ire_base_1024) : mad24_vv(oy + miq, white, ire_base_1024)) >> 10;
+                        if (NOISE) ire = LVV ? mad24_vvv(oy + miq, white64, ire_base_65536) : mad24_vv(oy + miq, white64, ire_base_65536);
+                        else ire = (LVV ? mad24_vvv(oy + miq, white, ire_base_1024) : mad24_vv(oy + miq, white, ire_base_1024)) >> 10;
                     } else {
                         const int mi = (oi * ccI) >> 4;
                         const int mq = (oq * ccQ) >> 4;
@@ -738,7 +749,7 @@ k_active(const crthip_params P, int n_fields, const unsigned char *__restrict__ 
                         if (FAST) {
                             /* ((byte - 0x7f) * noise) >> 8 added to ire: the product scaled by 256 so that the
                              * shift becomes "take the high word" and rides on the add (|noise| < 2^15 on this path) */
-                            ire = add_hiwords(ire, KN ? mad24_vvv(nb, noise256, neg_noise127_256) : mad24_vv(nb, noise256, neg_noise127_256));
+                            ire = add_hiwords(ire, KNV ? mad24_vvv(nb, noise256, neg_noise127_256) : mad24_vv(nb, noise256, neg_noise127_256));
                         } else {
                             ire += (nb * noise + neg_noise127) >> 8;
                         }
@@ -1501,6 +1512,36 @@ static void launch_active_sizes(crthip_ctx *c, const crthip_params *p, int n, co
     const block_order bo = make_block_order(items, c->act_order_env == -1 ? n : c->act_order_env);
     const dim3 ogrid(bo.grid);
     const bool wide_in = c->ac_tile_env ? c->ac_tile_env == 32 : c->ac_tile ? c->ac_tile == 32 : c->size_env.w_min >= 1280;
+    /* Sizes WITH knob records (crthip_fieldpass_sizes_knobs / crthip_stills_sizes_knobs; c->knob_recs as well): the SZ instantiations
+     * with KN (the batch's largest noise is not 0), LV (level records bound) and HU (hue records bound), in the three tile shapes below.
+     * The large signal tiles have no such instantiation (compile time: profiles/sizes_knobs_timing.txt) -- such a call takes the
+     * 64-byte pieces whatever its wave count, identical bytes.  A combined call that needs none of the three (noise 0 everywhere, nothing
+     * bound: the records then only reach the sync chain and the decoder) launches the plain SZ kernel, which looks for the size
+     * records in `reserved`: it gets a copy of the blob with the pointer there. */
+    crthip_params plain;
+    (void) plain;
+    if constexpr (S::CCS == 4) {
+        const bool lv = level_call(c), hu = hue_call(c);
+        if (c->knob_recs && !noise && !lv && !hu) {
+            plain = *p;
+            size_blob_set(&plain, size_blob_knobs_get(p));
+            p = &plain;                                            /* the plain launches below, with the copy */
+        } else if (c->knob_recs) {
+#define CRTHIP_LAUNCH_ACTIVE_SZK(I4, AC, KNV, LVV, HUV) \
+    hipLaunchKernelGGL((k_active<S, KNV, FAST, I4, true, AC, 16, 16, KNV, LVV, HUV, true>), ogrid, block, 0, c->stream, *p, n, img, extent, dst, lay.fstride, d_state, c->d_jump16, bo.K, bo.per, lay.pitch, lay.shift, wrapn)
+#define CRTHIP_LAUNCH_ACTIVE_SZK_TILE(KNV, LVV, HUV) \
+    do { if (!in4) CRTHIP_LAUNCH_ACTIVE_SZK(false, 16, KNV, LVV, HUV); else if (wide_in) CRTHIP_LAUNCH_ACTIVE_SZK(true, 32, KNV, LVV, HUV); else CRTHIP_LAUNCH_ACTIVE_SZK(true, 16, KNV, LVV, HUV); } while (0)
+            if (hu) {
+                if (lv) { if (noise) CRTHIP_LAUNCH_ACTIVE_SZK_TILE(true, true, true); else CRTHIP_LAUNCH_ACTIVE_SZK_TILE(false, true, true); }
+                else    { if (noise) CRTHIP_LAUNCH_ACTIVE_SZK_TILE(true, false, true); else CRTHIP_LAUNCH_ACTIVE_SZK_TILE(false, false, true); }
+            } else if (lv) {
+                if (noise) CRTHIP_LAUNCH_ACTIVE_SZK_TILE(true, true, false); else CRTHIP_LAUNCH_ACTIVE_SZK_TILE(false, true, false);
+            } else CRTHIP_LAUNCH_ACTIVE_SZK_TILE(true, false, false);
+#undef CRTHIP_LAUNCH_ACTIVE_SZK_TILE
+#undef CRTHIP_LAUNCH_ACTIVE_SZK
+            return;
+        }
+    }
 #define CRTHIP_LAUNCH_ACTIVE_SZ(NZ, FA, I4, AC, OTV, OLV) \
     hipLaunchKernelGGL((k_active<S, NZ, FA, I4, true, AC, OTV, OLV, false, false, false, true>), ogrid, block, 0, c->stream, *p, n, img, extent, dst, lay.fstride, d_state, c->d_jump16, bo.K, bo.per, lay.pitch, lay.shift, wrapn)
     if constexpr (FAST && S::CCS == 4) {

@@ -982,6 +982,8 @@ static int fieldpass_chunk(crthip_ctx *c, const crthip_params *p, int enc, int f
         knob_blob_set(&pk, c->knob_recs + first);
         if (level_call(c)) level_blob_set(&pk, level_blob_get(p) + first);
         if (hue_call(c)) hue_blob_set(&pk, hue_blob_get(p) + first);
+        /* ... and with mixed sizes as well (crthip_fieldpass_sizes_knobs): the size records' pointer, in its home of such a call */
+        if (c->size_recs) size_blob_knobs_set(&pk, c->size_recs + first);
         p = &pk;
     } else if (c->size_recs) {
         /* mixed sizes: likewise the size record of the chunk's first field; the images have no stride (istride == 0: img stays the
@@ -1258,6 +1260,45 @@ int crthip_fieldpass_sizes(crthip_ctx *c, const crthip_params *p, int n, const v
     return rc;
 }
 
+/* Sizes AND knob records: what both parents check, in their own words, and *q = the knob call's blob (knobs_blob: the bounds, the
+ * knob / level / hue pointers) with the size records' pointer in its home of such a call (size_blob_knobs_set, crt_dev.h).  The
+ * caller sets c->knob_recs and c->size_recs for the duration of its launches; sizes_knobs_done clears everything on every way out. */
+static int sizes_knobs_blob(crthip_ctx *c, const crthip_params *p, int n, const void *d_images, const crthip_size_rec *d_srecs,
+                            const crthip_sizes_env *senv, const crthip_knob_rec *d_recs, const crthip_knobs_env *env, crthip_params *q)
+{
+    crthip_params qs;
+    int rc = sizes_blob(c, p, n, d_images, d_srecs, senv, &qs);
+    if (rc) return rc;
+    rc = knobs_blob(c, p, n, d_recs, env, q);
+    if (rc) return rc;
+    size_blob_knobs_set(q, d_srecs);
+    return CRTHIP_OK;
+}
+static int sizes_knobs_done(crthip_ctx *c, int rc)
+{
+    c->knob_recs = nullptr;
+    c->size_recs = nullptr;
+    c->lev_on = 0;
+    c->hue_on = 0;
+    return rc;
+}
+
+int crthip_fieldpass_sizes_knobs(crthip_ctx *c, const crthip_params *p, int n, const void *d_images, void *d_out, size_t ostride,
+                                 crthip_state *d_state, const crthip_size_rec *d_srecs, const crthip_sizes_env *senv,
+                                 const crthip_knob_rec *d_recs, const crthip_knobs_env *env)
+{
+    int rc = check_params(c, p, n);
+    if (rc) return rc;
+    c->knob_recs = nullptr;
+    c->size_recs = nullptr;
+    crthip_params q;
+    rc = sizes_knobs_blob(c, p, n, d_images, d_srecs, senv, d_recs, env, &q);
+    if (rc) return sizes_knobs_done(c, rc);
+    c->knob_recs = d_recs;
+    c->size_recs = d_srecs;
+    return sizes_knobs_done(c, fieldpass_body(c, &q, n, d_images, 0, d_out, ostride, d_state));
+}
+
 /* ---- stills ---------------------------------------------------------------------------------------------------------------- */
 int crthip_stills_schedule(int interlaced, int first_field, int n_frames, crthip_pass *sched, int cap)
 {
@@ -1436,6 +1477,25 @@ int crthip_stills_sizes(crthip_ctx *c, const crthip_params *p, int n, const void
     rc = stills_body(c, &q, n, d_images, 0, d_out, ostride, d_state, n_passes, sched);
     c->size_recs = nullptr;
     return rc;
+}
+
+/* records k are still k's size AND look in every pass; with the call's largest noise 0 every distinct entry is encoded once with the
+ * blob of all the records (the SZ + LV / HU instantiations: a still's clean signal depends on its own size, levels and hue) */
+int crthip_stills_sizes_knobs(crthip_ctx *c, const crthip_params *p, int n, const void *d_images, void *d_out, size_t ostride,
+                              crthip_state *d_state, int n_passes, const crthip_pass *sched,
+                              const crthip_size_rec *d_srecs, const crthip_sizes_env *senv,
+                              const crthip_knob_rec *d_recs, const crthip_knobs_env *env)
+{
+    int rc = check_params(c, p, n);
+    if (rc) return rc;
+    c->knob_recs = nullptr;
+    c->size_recs = nullptr;
+    crthip_params q;
+    rc = sizes_knobs_blob(c, p, n, d_images, d_srecs, senv, d_recs, env, &q);
+    if (rc) return sizes_knobs_done(c, rc);
+    c->knob_recs = d_recs;
+    c->size_recs = d_srecs;
+    return sizes_knobs_done(c, stills_body(c, &q, n, d_images, 0, d_out, ostride, d_state, n_passes, sched));
 }
 
 unsigned crthip_table_generation(const crthip_ctx *c) { return c ? c->table_gen : 0u; }

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Finished stills for a folder of images: what the reference's `ntsc` program (crt_main.c) writes for every file, in batches.
 
-    python tools/stills_dir.py [--one-call] [-m|f|p|r] OUTW OUTH NOISE HUE IN_DIR OUT_DIR
+    python tools/stills_dir.py [--one-call [--looks FILE]] [-m|f|p|r] OUTW OUTH NOISE HUE IN_DIR OUT_DIR
 
 The flags are `ntsc`'s (crt_main.c:95-110): m monochrome, f start at the odd field, p progressive, r raw (no scaling); o is accepted
 and ignored (existing files are overwritten), a (analog dumps) is not available.  Every P6 .ppm of IN_DIR is read; files of equal
@@ -11,6 +11,11 @@ distinct field / frame of the schedule is encoded once for the batch); OUT_DIR/<
 --one-call: the files are NOT grouped by size; the whole folder (MAX_BATCH files at a time) goes through one crthip_stills_sizes call
 (CRT.stills_sizes: every still with its own w and h), with byte-identical output files.  Not with r: raw images are refused there
 (the signal rectangle then depends on the image size).  The default stays the grouped path.
+
+--one-call --looks FILE: every picture with its own look -- FILE holds one line per picture, the file name and eight integers (noise,
+mon_hue, saturation, brightness, contrast, black_point, white_point, hue), which replace NOISE, HUE and crt_init's defaults for that
+picture; the folder goes through one crthip_stills_sizes_knobs call (CRT.stills_sizes_knobs).  A file that gives every picture
+NOISE, HUE and the defaults (default_look) writes what --one-call alone writes.
 
 PPM reading and writing are numpy: ppm_read24 / ppm_write24 (ppm_rw.c) restated.  The pixels travel as RGB24 in both directions
 (CRTHIP_FMT_RGB): the encoder reads the same r, g, b whatever the byte order, and the colour bytes of the decoder's blended BGRA
@@ -110,11 +115,70 @@ def convert_mixed(crtlib, torch, imgs, outw, outh, noise, hue, opt):
     return out
 
 
+LOOK_NAMES = ("noise", "mon_hue", "saturation", "brightness", "contrast", "black_point", "white_point", "hue")
+
+
+def default_look(noise, hue):
+    """the look the command line gives every picture: NOISE and HUE beside crt_init's defaults (crt_core.c:263-289)"""
+    return (noise, 0, 10, 0, 180, 0, 100, hue)
+
+
+def parse_looks(path, names):
+    """--looks FILE: one line per picture -- the file name and eight integers, LOOK_NAMES in this order; empty lines and lines
+    starting with '#' are skipped.  Returns an (n, 8) int32 array in the order of ``names``; a picture without a line, a line for
+    no picture, a name given twice or a malformed line is an error.  Noise below 0 becomes 0 and the hue is reduced by C's % 360,
+    as the command line's are."""
+    looks = {}
+    with open(path) as f:
+        for ln, line in enumerate(f, 1):
+            tok = line.split()
+            if not tok or tok[0].startswith("#"):
+                continue
+            if len(tok) != 1 + len(LOOK_NAMES):
+                raise SystemExit("%s:%d: a file name and %d integers are needed (%s)" % (path, ln, len(LOOK_NAMES), " ".join(LOOK_NAMES)))
+            try:
+                vals = [int(t) for t in tok[1:]]
+            except ValueError:
+                raise SystemExit("%s:%d: not an integer" % (path, ln))
+            if tok[0] in looks:
+                raise SystemExit("%s:%d: %s has a look already" % (path, ln, tok[0]))
+            vals[0] = max(vals[0], 0)
+            vals[7] = int(np.fmod(vals[7], 360))
+            looks[tok[0]] = vals
+    missing = [n for n in names if n not in looks]
+    extra = sorted(set(looks) - set(names))
+    if missing or extra:
+        raise SystemExit("%s: no look for %s; no picture for %s" % (path, ", ".join(missing) or "-", ", ".join(extra) or "-"))
+    return np.array([looks[n] for n in names], dtype=np.int32).reshape(len(names), len(LOOK_NAMES))
+
+
+def convert_mixed_looks(crtlib, torch, imgs, looks, outw, outh, opt):
+    """convert_mixed with row k of ``looks`` ((n, 8), LOOK_NAMES) as picture k's look, in ONE stills_sizes_knobs call"""
+    crt = crtlib.CRT(len(imgs), outw, outh, crtlib.FMT_RGB, "ntsc", device=0)
+    crt.blend = crt.scanlines = 1                                   # crt_main.c:235-236
+    s = crtlib.Settings(None, format=crtlib.FMT_RGB, raw=0, as_color=opt["docolor"], hue=0, spare_row=False)
+    data = [torch.from_numpy(np.array(px)).to(crt.dev) for px in imgs]
+    crt.stills_sizes_knobs(data, looks, interlaced=not opt["progressive"], first_field=opt["field"], frames=4, settings=s)
+    crt.synchronize()
+    out = crt.out.cpu().numpy()
+    crt.close()
+    return out
+
+
 def main(argv):
     args = argv[1:]
     one_call = "--one-call" in args
     if one_call:
         args.remove("--one-call")
+    looks_file = None
+    if "--looks" in args:
+        i = args.index("--looks")
+        if i + 1 >= len(args):
+            raise SystemExit(__doc__)
+        looks_file = args[i + 1]
+        del args[i:i + 2]
+        if not one_call:
+            raise SystemExit("--looks goes with --one-call")
     opt = parse_flags(args.pop(0)) if args and args[0].startswith("-") else parse_flags("")
     if len(args) != 6:
         raise SystemExit(__doc__)
@@ -135,9 +199,13 @@ def main(argv):
     done = 0
     if one_call:
         files = [(name, px) for _, group in sorted(by_size.items()) for name, px in group]
+        looks = parse_looks(looks_file, [name for name, _ in files]) if looks_file else None
         for lo in range(0, len(files), MAX_BATCH):
             part = files[lo:lo + MAX_BATCH]
-            out = convert_mixed(crtlib, torch, [px for _, px in part], outw, outh, noise, hue, opt)
+            if looks is not None:
+                out = convert_mixed_looks(crtlib, torch, [px for _, px in part], looks[lo:lo + MAX_BATCH], outw, outh, opt)
+            else:
+                out = convert_mixed(crtlib, torch, [px for _, px in part], outw, outh, noise, hue, opt)
             for (name, _), pic in zip(part, out):
                 write_ppm(os.path.join(out_dir, os.path.splitext(name)[0] + ".ppm"), pic)
             done += len(part)
