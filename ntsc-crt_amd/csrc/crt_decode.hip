@@ -7,7 +7,7 @@
  * ORed every field's own floor into its lines' tier flags. */
 int crt_decoder_min_tier(const crthip_ctx *c, const crthip_params *p)
 {
-    const int fl = knob_pic_call(c) ? c->knob_floor_lo : crt_setup_decoder_floor(p, p->bright, p->contrast);
+    const int fl = c->call.pic ? c->call.floor_lo : crt_setup_decoder_floor(p, p->bright, p->contrast);
     if (c->force_exact || fl >= 3) return 3;
     if (c->no_tier0 || c->no_loskip) return 2;  /* crthip_set_exact(2) / (3): keep the I/Q low cascades = the 24-bit tier */
     return fl;
@@ -23,7 +23,7 @@ bool crt_decode_fstages(crthip_ctx *c, const crthip_params *p, int min_tier, FSt
     memset(fs, 0, sizeof *fs);
     c->last_fstage = 0;
     /* picture knobs: the integer stages (the binade proof below is for ONE |bright|) */
-    if (!c->dec_float || min_tier > 1 || knob_pic_call(c)) return false;
+    if (!c->dec_float || min_tier > 1 || c->call.pic) return false;
     crthip_fstages q;
     if (crthip_float_stages_query(p, 0, &q) != 1) return false;
     for (int k = 0; k < 4; k++) {
@@ -76,7 +76,7 @@ int crt_run_decode(crthip_ctx *c, const crthip_params *p, int n, const signed ch
                             !(n >= WIDE_SHAPE_MIN_FIELDS && !p->bloom && crt_decode_wide_ok(c, p, decoder_min_tier(c, p), wide_px))));
     if (rows_shape) return crt_run_decode_rows(c, p, n, d_inp, d_lines, d_out, ostride, fstride);
     /* picture knobs on the lane-per-scanline shape: the PK instantiations of k_decode (crt_decode_pk.hip; the bloom build's: crt_decode3.hip) */
-    if (knob_pic_call(c) && !p->bloom) return crt_run_decode_pk(c, p, n, d_inp, d_lines, d_out, ostride, fstride, wide_px);
+    if (c->call.pic && !p->bloom) return crt_run_decode_pk(c, p, n, d_inp, d_lines, d_out, ostride, fstride, wide_px);
     if (p->bloom) return crt_run_decode_bloom_lanes(c, p, n, d_inp, d_lines, d_out, ostride, decoder_min_tier(c, p), fstride);
     /* FIR build: the filters only add, their outputs stay inside the hull of the inputs, so the 24-bit envelope
      * of tier 2 carries over (tier 4); beyond it the exact instantiation (tier 5) */

@@ -306,7 +306,7 @@ int crt_run_decode_rows(crthip_ctx *c, const crthip_params *p, int n, const sign
         ProfScope ps(c, CRTHIP_K_DECODE);
         for (int rank = 0; rank < passes; rank++) {
 #define CRTHIP_LAUNCH_ROWS_T(B3, TSV) \
-    do { if constexpr (S::CCS == 4) { if (knob_pic_call(c)) { /* picture knobs: bright / contrast per scanline */ \
+    do { if constexpr (S::CCS == 4) { if (c->call.pic) { /* picture knobs: bright / contrast per scanline */ \
              if (narrow_ok) hipLaunchKernelGGL((k_decode_row<S, true, B3, TSV, true>), dim3((total + 3) / 4), dim3(64), 0, c->stream, *p, n, d_inp, fstride, d_lines, o, ostride, rank, 0); \
              hipLaunchKernelGGL((k_decode_row<S, false, B3, TSV, true>), dim3((total + 1) / 2), dim3(64), 0, c->stream, *p, n, d_inp, fstride, d_lines, o, ostride, rank, narrow_ok ? 0 : 1); \
              break; } } \

@@ -153,7 +153,7 @@ int crt_run_decode_bloom_lanes(crthip_ctx *c, const crthip_params *p, int n, con
             unsigned char *o = (unsigned char *) d_out;
             for (int rank = 0; rank < passes; rank++) {
 #define CRTHIP_LAUNCH_BLOOM(TG, B3) \
-    do { if constexpr (S::CCS == 4) { if (knob_pic_call(c)) { /* picture knobs: bright / contrast per lane (crt_decode_lane.h, PK) */ \
+    do { if constexpr (S::CCS == 4) { if (c->call.pic) { /* picture knobs: bright / contrast per lane (crt_decode_lane.h, PK) */ \
              if (wide) hipLaunchKernelGGL((k_decode<S, TG, B3, 32, true, false, true>), grid, block, 0, c->stream, *p, n, d_inp, fstride, d_lines, o, ostride, min_tier, rank, (const int *) perm, 0, 0, fsa); \
              else hipLaunchKernelGGL((k_decode<S, TG, B3, 16, true, false, true>), grid, block, 0, c->stream, *p, n, d_inp, fstride, d_lines, o, ostride, min_tier, rank, (const int *) perm, 0, 0, fsa); \
              break; } } \

@@ -298,7 +298,7 @@ int crt_run_decode_wide(crthip_ctx *c, const crthip_params *p, int n, const sign
             const int nblk = (total + lpw - 1) / lpw;
             const block_order bo = make_block_order(nblk, c->wide_order_env == 0 || c->wide_order_env == -1 ? n : c->wide_order_env);
             const dim3 ogrid(bo.grid);
-            if (knob_pic_call(c)) {                         /* picture knobs: bright / contrast of the wave's field */
+            if (c->call.pic) {                         /* picture knobs: bright / contrast of the wave's field */
                 if (lpw == 8)
                     hipLaunchKernelGGL((k_decode_wide<S, 8, true>), ogrid, block, 0, c->stream, *p, n, d_inp, fstride, d_lines, (unsigned char *) d_out, ostride,
                                        min_tier, rank, n_px, ppos_end, bo.K, bo.per);

@@ -440,95 +440,60 @@ __device__ __forceinline__ unsigned lcg_at(const uint2 *__restrict__ jump16, uns
     return rn;
 }
 
-/* Per-field knobs (crthip_fieldpass_knobs, crthip_sequence_knobs / _sets_knobs, the phases after crthip_seq_bind_knobs).  The kernels that apply the channel noise or fold the monitor hue and saturation into the
- * line table have a second instantiation, KN, that takes the value from the field's crthip_knob_rec instead of the parameter blob.
- * Their signatures do not change: the blob a knob launch passes is the library's own copy, whose `reserved` words carry the device
- * pointer to the record of the launch's field 0 (crt_host.hip, fieldpass_chunk / knobs_blob), and whose noise / saturation are the batch's
- * bounds -- what the launch code decides by.  crthip_ctx.knob_recs != nullptr says that such a call is under way. */
-static inline void knob_blob_set(crthip_params *q, const crthip_knob_rec *d_recs)
+/* Per-field records.  A record call (crt_host.hip: call_begin fills crthip_ctx.call, CallScope resets it) launches further
+ * instantiations of the kernels -- KN, PK, LV, HU, SZ -- that take a value from the record of their field instead of the parameter
+ * blob.  No kernel signature changes for that: the blob such a launch passes is the library's own copy, whose value words hold the
+ * call's bounds where the launch code decides by them (noise, saturation), and in which words that the instantiation does not read
+ * as values carry the device pointer to the record of the LAUNCH's field 0.  launch_blob (crt_host.hip) is the one place that
+ * writes these pointers; the __device__ getters below are the one place that reads them.
+ *
+ *   records                         blob words in a           read by (getter)                                the launch code reads
+ *                                   knob | sizes | both call                                                  instead
+ *   crthip_knob_rec                 reserved | -- | reserved   KN: k_active*, k_margin*, k_noise, k_vhs_*,    call.knobs, call.pic, call.floor_lo,
+ *    (crthip_knobs_prepare*)                                   k_hsync_wave, k_bloom; PK: the decoders        call.loskip (sync_blob); p->noise and
+ *                                                              (knob_blob_recs)                               p->saturation = the env's bounds
+ *   crthip_level_rec                white + ire_base in a      LV: k_active, k_active_row                     call.levels, call.lev_env
+ *    (crthip_bind_levels)           knob and a both call       (level_blob_recs)                              (encoder_fast_ok)
+ *   crthip_hue_rec                  burst[0][0..1] in a        HU: k_active, k_active_row, k_margin*,         call.hues; call.burst0 = the caller's two
+ *    (crthip_bind_hues)             knob and a both call       k_encoder_state (hue_blob_recs)                words (crt_run_encoder_prepare)
+ *   crthip_size_rec                 -- | reserved |            SZ: k_active (size_blob_recs; with KN, LV      call.sizes, call.size_env; istride = the
+ *    (crthip_sizes_prepare)         col_step_lo + _hi          or HU: size_blob_recs_knobs)                   extent of the image buffer
+ *
+ * The col_step words are free in a call with size records: the SZ kernels take col_step from the record, and crthip_params_finalize's
+ * check of them has passed on the caller's blob before the copy is made (a device pointer is never the 0 check_encoder looks for).
+ * The one host-side reader of a blob's pointer is launch_active_sizes (crt_encode.hip): it sees a chunk's blob, not the chunk's first
+ * field, so it takes the size records' pointer of a both call from there (size_blob_knobs_get) when it hands the plain SZ kernel a
+ * copy with that pointer back in `reserved`. */
+static_assert(offsetof(crthip_params, ire_base) == offsetof(crthip_params, white) + sizeof(int), "white and ire_base are neighbours: one device pointer");
+static_assert(offsetof(crthip_params, col_step_hi) == offsetof(crthip_params, col_step_lo) + sizeof(unsigned), "col_step_lo and _hi are neighbours: one device pointer");
+static_assert(sizeof(((crthip_params *) 0)->reserved) == sizeof(void *), "a device pointer fits crthip_params.reserved");
+static_assert(sizeof(crthip_hue_rec) == 640 && offsetof(crthip_hue_rec, modI) == sizeof(((crthip_params *) 0)->burst), "crthip_hue_rec: the three tables of crthip_params");
+static_assert(sizeof(crthip_size_rec) == 32 && sizeof(crthip_size) == 16, "crthip_size_rec: 32 bytes, crthip_size: 16");
+/* a device pointer into two neighbouring 32-bit words of a blob, low word first */
+static inline void blob_put_ptr(void *words, const void *d_ptr)
 {
-    static_assert(sizeof(q->reserved) == sizeof(d_recs), "a device pointer fits crthip_params.reserved");
-    memcpy(q->reserved, &d_recs, sizeof(d_recs));
+    static_assert(sizeof(d_ptr) == 2 * sizeof(int), "a device pointer fits two words of crthip_params");
+    memcpy(words, &d_ptr, sizeof(d_ptr));
+}
+static inline const crthip_size_rec *size_blob_knobs_get(const crthip_params *q)
+{
+    return (const crthip_size_rec *) (((unsigned long long) q->col_step_hi << 32) | q->col_step_lo);
 }
 __device__ __forceinline__ const crthip_knob_rec *knob_blob_recs(const crthip_params &P)
 {
     return (const crthip_knob_rec *) (((unsigned long long) (unsigned) P.reserved[1] << 32) | (unsigned) P.reserved[0]);
 }
-
-/* Level knobs (crthip_knobs_prepare7, crthip_bind_levels): black point and white point per field.  The active-video kernels have a
- * further instantiation, LV, that takes white and ire_base from the field's crthip_level_rec.  Again no signature changes: in the
- * library's copy of the blob of such a call the words `white` and `ire_base` -- which the LV kernels do not read as values, and the
- * launch code replaces by the bounds of crthip_levels_env (crthip_ctx.lev_*) -- carry the device pointer to the level record of the
- * launch's field 0, as `reserved` carries the knob records'.  crthip_ctx.lev_on says that such a call is under way (level_call). */
-static_assert(offsetof(crthip_params, ire_base) == offsetof(crthip_params, white) + sizeof(int), "white and ire_base are neighbours: one device pointer");
-static inline void level_blob_set(crthip_params *q, const crthip_level_rec *d_levs)
-{
-    static_assert(2 * sizeof(int) == sizeof(d_levs), "a device pointer fits crthip_params.white + .ire_base");
-    memcpy(&q->white, &d_levs, sizeof(int));
-    memcpy(&q->ire_base, (const char *) &d_levs + sizeof(int), sizeof(int));
-}
-static inline const crthip_level_rec *level_blob_get(const crthip_params *q)
-{
-    return (const crthip_level_rec *) (((unsigned long long) (unsigned) q->ire_base << 32) | (unsigned) q->white);
-}
 __device__ __forceinline__ const crthip_level_rec *level_blob_recs(const crthip_params &P)
 {
     return (const crthip_level_rec *) (((unsigned long long) (unsigned) P.ire_base << 32) | (unsigned) P.white);
-}
-
-/* Hue knob (crthip_knobs_prepare8, crthip_bind_hues): the encoder hue per field.  Every kernel that reads the carrier tables on a path
- * a knob call reaches has a further instantiation, HU, that takes them from the field's crthip_hue_rec.  No signature changes here
- * either: in the library's copy of the blob of such a call the words burst[0][0] and burst[0][1] -- which the HU kernels do not read
- * as values -- carry the device pointer to the hue record of the launch's field 0.  crthip_ctx.hue_on says that such a call is under
- * way (hue_call); crthip_ctx.hue_burst0 keeps the two words the pointer replaced, for the one reader of the blob's own burst table
- * that remains (the skeleton cache, crt_run_encoder_prepare). */
-static_assert(sizeof(crthip_hue_rec) == 640 && offsetof(crthip_hue_rec, modI) == sizeof(((crthip_params *) 0)->burst), "crthip_hue_rec: the three tables of crthip_params");
-static inline void hue_blob_set(crthip_params *q, const crthip_hue_rec *d_hues)
-{
-    static_assert(2 * sizeof(int) == sizeof(d_hues), "a device pointer fits crthip_params.burst[0][0..1]");
-    memcpy(&q->burst[0][0], &d_hues, 2 * sizeof(int));
-}
-static inline const crthip_hue_rec *hue_blob_get(const crthip_params *q)
-{
-    return (const crthip_hue_rec *) (((unsigned long long) (unsigned) q->burst[0][1] << 32) | (unsigned) q->burst[0][0]);
 }
 __device__ __forceinline__ const crthip_hue_rec *hue_blob_recs(const crthip_params &P)
 {
     return (const crthip_hue_rec *) (((unsigned long long) (unsigned) P.burst[0][1] << 32) | (unsigned) P.burst[0][0]);
 }
-
-/* Mixed image sizes (crthip_sizes_prepare, crthip_fieldpass_sizes / crthip_stills_sizes): w, h, col_step and the image's offset per
- * field.  The lane-per-row active-video kernel has a further instantiation, SZ, that takes them from the field's crthip_size_rec.
- * No signature changes: a sizes call carries no knob records (crt_hip.h, OUT OF SCOPE), so the blob's `reserved` words carry the
- * device pointer to the size record of the launch's field 0 exactly as they carry the knob records' in a knob call, and the
- * `istride` argument of the launch -- a sizes call has no image stride -- carries the extent of the image buffer, against which
- * every wavefront checks its record (size_rec_checked).  crthip_ctx.size_recs != nullptr says that such a call is under way. */
-static_assert(sizeof(crthip_size_rec) == 32 && sizeof(crthip_size) == 16, "crthip_size_rec: 32 bytes, crthip_size: 16");
-static inline void size_blob_set(crthip_params *q, const crthip_size_rec *d_srecs)
-{
-    static_assert(sizeof(q->reserved) == sizeof(d_srecs), "a device pointer fits crthip_params.reserved");
-    memcpy(q->reserved, &d_srecs, sizeof(d_srecs));
-}
 __device__ __forceinline__ const crthip_size_rec *size_blob_recs(const crthip_params &P)
 {
     return (const crthip_size_rec *) (((unsigned long long) (unsigned) P.reserved[1] << 32) | (unsigned) P.reserved[0]);
-}
-/* Sizes WITH knob records (crthip_fieldpass_sizes_knobs / crthip_stills_sizes_knobs): `reserved` is taken by the knob records, white /
- * ire_base by the levels, burst[0][0..1] by the hues.  The size records' pointer of such a call lives in col_step_lo / _hi -- words a
- * sizes call does not read as values (the SZ kernels take col_step from the record; crthip_params_finalize's check of them has passed
- * on the caller's blob before the library's copy is made, and a device pointer is never the 0 check_encoder looks for).  The only
- * readers are k_active's SZ instantiations with KN, LV or HU and the launch code in front of them (launch_active_sizes, which hands the
- * plain SZ kernel a copy with the pointer back in `reserved`). */
-static_assert(offsetof(crthip_params, col_step_hi) == offsetof(crthip_params, col_step_lo) + sizeof(unsigned), "col_step_lo and _hi are neighbours: one device pointer");
-static inline void size_blob_knobs_set(crthip_params *q, const crthip_size_rec *d_srecs)
-{
-    static_assert(2 * sizeof(unsigned) == sizeof(d_srecs), "a device pointer fits crthip_params.col_step_lo + _hi");
-    memcpy(&q->col_step_lo, &d_srecs, sizeof(unsigned));
-    memcpy(&q->col_step_hi, (const char *) &d_srecs + sizeof(unsigned), sizeof(unsigned));
-}
-static inline const crthip_size_rec *size_blob_knobs_get(const crthip_params *q)
-{
-    return (const crthip_size_rec *) (((unsigned long long) q->col_step_hi << 32) | q->col_step_lo);
 }
 __device__ __forceinline__ const crthip_size_rec *size_blob_recs_knobs(const crthip_params &P)
 {
@@ -543,8 +508,6 @@ __device__ __forceinline__ int uniform_rec_int(const int *p)
 }
 #include "crt_size_guard.h"    /* size_view, size_rec_checked, size_col_clamped: plain C++, also compiled for the host by tests/test_sizes_cpu.py */
 
-/* Picture knobs (crthip_knobs_prepare5): is a call with such records under way?  The decoders then launch their PK instantiations */
-static inline bool knob_pic_call(const crthip_ctx *c);
 /* the tier flags a field's floor (crthip_knob_rec.tier_floor: 0, 2 or 3) puts on each of its lines -- what the decoders (and, min_tier >= 4,
  * their FIR tiers) read as "24-bit tier" / "exact tier" */
 __device__ __forceinline__ int tier_floor_flags(int tier_floor)
@@ -633,6 +596,24 @@ __host__ __device__ constexpr int vhs_tail_start(int input_size, int hres)
 /* host side: context, dispatch by system, C ABI                               */
 /* ------------------------------------------------------------------------- */
 #define CRTHIP_MAX_RETIRED 64
+/* The records of the call in flight: everything the launch code may ask about them.  Each pointer is the caller's device array (the
+ * record of the call's field 0), or nullptr: none of that kind, so a value-initialised rec_call IS the uniform call.  crt_host.hip's
+ * call_begin fills crthip_ctx.call once the call's records and envs have passed their checks, CallScope resets it on every way out,
+ * and nothing else writes it. */
+struct rec_call {
+    const crthip_knob_rec *knobs;     /* noise, monitor hue, saturation (and bloom's max_e) per field: the KN instantiations */
+    const crthip_level_rec *levels;   /* a knob call with level records bound (crthip_bind_levels): the encoder's LV instantiations */
+    const crthip_hue_rec *hues;       /* a knob call with hue records bound (crthip_bind_hues): the encoder's HU instantiations */
+    const crthip_size_rec *sizes;     /* image sizes per field: k_active's SZ instantiations */
+    crthip_levels_env lev_env;        /* the bounds of `levels`: what encoder_fast_ok decides by in place of p->white / p->ire_base */
+    crthip_sizes_env size_env;        /* the bounds of `sizes`: what the encoder's launch code decides by in place of p->w */
+    int loskip;                       /* knobs: the sync chain's no-low-cascade bound, from crthip_knobs_env.loskip_wave_max (sync_blob) */
+    int pic;                          /* knobs: the records carry picture knobs (crthip_knobs_prepare5) -- the sync kernel ORs every field's tier
+                                         floor into its lines' flags, the decoders' PK instantiations read bright / contrast per field */
+    int floor_lo;                     /* ... and the smallest tier floor of the fields: what crt_decoder_min_tier starts from then */
+    int burst0[2];                    /* hues: the caller's burst[0][0..1], whose place in the blob the records' pointer takes -- for the one
+                                         reader of the blob's own burst table that remains (the skeleton cache, crt_run_encoder_prepare) */
+};
 struct crthip_ctx {
     int device;
     int system, pattern;
@@ -705,22 +686,14 @@ struct crthip_ctx {
     int last_fstage;            /* the last decoder call launched the float-stage kernels (crthip_float_stages_used) */
     int sig_tile_env;           /* CRTHIP_SIG_TILE = 16 | 32 | 64: pins k_active's small / large signal tile (A/B measurements); 0 = by batch size */
     int overlap_chunks;         /* crthip_fieldpass: chunks alternating between two streams (1 = off) */
-    const crthip_knob_rec *knob_recs;   /* a *_knobs call (or a phase with bound records) under way: the caller's device records (field 0 of the call), else nullptr */
-    int knob_loskip;            /* ... and its crthip_knobs_env.loskip_wave_max */
-    int knob_pic;               /* ... its records carry picture knobs (crthip_knobs_prepare5): the sync kernel ORs every field's tier floor into its
-                                   lines' flags, the decoders' PK instantiations read bright / contrast from the record of each line's field */
-    int knob_floor_lo;          /* ... and the smallest tier floor of its fields: what decoder_min_tier starts from then */
+    rec_call call;              /* the records of the call in flight (above) */
+    /* what outlives calls: the bindings.  Read by call_begin alone (crt_host.hip), which copies what a call uses into `call` */
     const crthip_knob_rec *seq_knob_recs;   /* crthip_seq_bind_knobs: the shard's records for crthip_seq_encode / _sync / _decode (nullptr: none bound) */
     crthip_knobs_env seq_knob_env;          /* ... and the library's copy of their bounds */
     const crthip_level_rec *lev_recs;       /* crthip_bind_levels: the caller's device level records for the knob entry points (nullptr: none bound) */
     crthip_levels_env lev_env;              /* ... and the library's copy of their bounds */
-    int lev_on;                             /* the knob call under way (knob_recs != nullptr) runs with them: the encoder launches its LV instantiations */
     const crthip_hue_rec *hue_recs;         /* crthip_bind_hues: the caller's device hue records for the knob entry points (nullptr: none bound) */
     crthip_hues_env hue_env;                /* ... and the library's copy of their env */
-    int hue_on;                             /* the knob call under way runs with them: the encoder launches its HU instantiations */
-    int hue_burst0[2];                      /* ... and the caller's burst[0][0..1], which the records' pointer replaced in the blob (hue_blob_set) */
-    const crthip_size_rec *size_recs;       /* a *_sizes call under way: the caller's device size records (field 0 of the call), else nullptr */
-    crthip_sizes_env size_env;              /* ... and the library's copy of their bounds: what the encoder's launch code decides by in place of p->w */
     hipStream_t aux_stream;
     hipEvent_t ev_fork, ev_join, ev_chunk[CRTHIP_MAX_CHUNKS];
     hipEvent_t ev_mfork, ev_mjoin;   /* the margin kernel beside the active-video kernel (crt_encode.hip, launch_encoder) */
@@ -732,10 +705,6 @@ struct crthip_ctx {
     int npend, cappend;
     char err[256];
 };
-
-static inline bool knob_pic_call(const crthip_ctx *c) { return c->knob_recs != nullptr && c->knob_pic != 0; }
-static inline bool level_call(const crthip_ctx *c) { return c->knob_recs != nullptr && c->lev_on != 0; }
-static inline bool hue_call(const crthip_ctx *c) { return c->knob_recs != nullptr && c->hue_on != 0; }
 
 static inline int set_err(crthip_ctx *c, int code, const char *what, hipError_t e)
 {

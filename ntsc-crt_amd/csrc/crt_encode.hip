@@ -488,7 +488,7 @@ k_active(const crthip_params P, int n_fields, const unsigned char *__restrict__ 
     size_view sz = { P.w, P.h, 0ull, 0ull };
     if constexpr (SZ) {
         static_assert(!S::IS_NES, "sizes: RGB input (crt_hip.h, OUT OF SCOPE)");
-        static_assert(!(KN || LV || HU) || S::CCS == 4, "sizes with knob records: the 4-sample systems (knobs_blob refuses the PV-1000)");
+        static_assert(!(KN || LV || HU) || S::CCS == 4, "sizes with knob records: the 4-sample systems (call_begin refuses the PV-1000)");
         const int per_field = (rows + 63) >> 6;
         const bool item_ok = item < n_fields * per_field;
         f_ = item_ok ? item / per_field : 0;                                    /* wave-uniform */
@@ -1326,10 +1326,10 @@ static bool encoder_fast_ok(const crthip_ctx *c, const crthip_params *p)
 {
     /* a call with level records (crthip_bind_levels): the batch's largest |white| and |ire_base| decide -- one field over the bound
      * sends the whole call to the exact kernels (p->white / p->ire_base carry the records' pointer then, crt_dev.h) */
-    const bool lv = level_call(c);
-    const int wh = lv ? c->lev_env.white_abs_max : p->white < 0 ? -p->white : p->white;
+    const bool lv = c->call.levels;
+    const int wh = lv ? c->call.lev_env.white_abs_max : p->white < 0 ? -p->white : p->white;
     const int nz = p->noise < 0 ? -p->noise : p->noise;
-    const int ib = lv ? c->lev_env.ire_base_abs_max : p->ire_base < 0 ? -p->ire_base : p->ire_base;
+    const int ib = lv ? c->call.lev_env.ire_base_abs_max : p->ire_base < 0 ? -p->ire_base : p->ire_base;
     /* noise * 256 is a 24-bit multiplier in k_active; (y + i + q) * white * 64 + (ire_base << 16) must not wrap: |y + i + q| <= 1020 +
      * 609 + 534 (8-bit pixels through crt_ntsc.c:307-309, carriers <= 16 / 16), so 2163 * 2^13 * 64 + 2^13 * 2^16 < 2^31.  (Rounds 1-5
      * let white up to 2^23 into the fast kernels, where the product could wrap differently from the reference's; nothing sane is near.) */
@@ -1337,7 +1337,7 @@ static bool encoder_fast_ok(const crthip_ctx *c, const crthip_params *p)
     if (p->flags & CRTHIP_F_HIPASS) ok = false;                   /* the debug build's high-pass lives in the exact kernels */
     /* (a call with hue records, crthip_bind_hues: crthip_knobs_prepare8 has checked every field's carriers against this very bound
      * and refuses a batch with one outside it; the blob's own tables are not the call's) */
-    for (int r = 0; r < CRTHIP_CARRIER_ROWS && !hue_call(c); r++)  /* ... and so are the carriers * 4096 */
+    for (int r = 0; r < CRTHIP_CARRIER_ROWS && !c->call.hues; r++)  /* ... and so are the carriers * 4096 */
         for (int k = 0; k < CRTHIP_MAX_CCS; k++)
             ok = ok && p->modI[r][k] > -2048 && p->modI[r][k] < 2048 && p->modQ[r][k] > -2048 && p->modQ[r][k] < 2048;
     if (S::BANDLIMIT)                                              /* the forms of the 64-bit low-passes (k_active) */
@@ -1355,7 +1355,7 @@ static void launch_active(crthip_ctx *c, const crthip_params *p, int n, const vo
                           signed char *dst, const crthip_state *d_state, const sig_layout &lay)
 {
     if constexpr (FULL && !S::IS_NES) {
-        if (c->size_recs) { launch_active_sizes<S, FAST>(c, p, n, d_images, dst, d_state, lay); return; }
+        if (c->call.sizes) { launch_active_sizes<S, FAST>(c, p, n, d_images, dst, d_state, lay); return; }
     }
     const int wrapn = lay.pitch != S::HRES ? lay.wrap : 0;      /* flat lines: a row that runs over its line's end simply continues */
     ProfScope ps(c, CRTHIP_K_ACTIVE);
@@ -1367,7 +1367,7 @@ static void launch_active(crthip_ctx *c, const crthip_params *p, int n, const vo
             /* the sample table depends on the black / white point only: rebuilt when those change, always on the
              * context's main stream (crt_run_encoder_prepare), never concurrently with a reader */
             if constexpr (FULL) {
-                if (p->noise != 0 && c->knob_recs) {
+                if (p->noise != 0 && c->call.knobs) {
                     hipLaunchKernelGGL((k_active_nes<S, true, true, 16, true>), grid, block, 0, c->stream, *p, n, img, istride, dst, lay.fstride, d_state, c->d_jump16, c->d_nes_tab, lay.pitch, lay.shift, wrapn);
                     return;
                 }
@@ -1380,16 +1380,16 @@ static void launch_active(crthip_ctx *c, const crthip_params *p, int n, const vo
         }
     }
     const bool noise = FULL && p->noise != 0;
-    const bool kn = noise && c->knob_recs;                       /* per-field noise: the KN instantiations (fused path only) */
+    const bool kn = noise && c->call.knobs;                       /* per-field noise: the KN instantiations (fused path only) */
     /* per-field black / white point: the LV instantiations -- every shape a knob call reaches below has one, with the per-field noise
      * (kn: a level call is a knob call) or without any (the batch's largest noise is 0; the clean field of the rand()-noise VHS build
-     * and of CRT_DO_VSYNC 0).  The PPU encoder and the 5-sample system have none: such a call is refused (crt_host.hip, knobs_blob) */
+     * and of CRT_DO_VSYNC 0).  The PPU encoder and the 5-sample system have none: such a call is refused (crt_host.hip, call_begin) */
     constexpr bool LVS = FULL && !S::IS_NES && S::CCS == 4;
-    const bool lv = LVS && level_call(c);
+    const bool lv = LVS && c->call.levels;
     (void) lv;
     /* per-field encoder hue: the HU instantiations, of the same shapes, with the level records (lv) or with the blob's white and
      * ire_base (a hue-only binding) */
-    const bool hu = LVS && hue_call(c);
+    const bool hu = LVS && c->call.hues;
     (void) hu;
     if constexpr (!S::IS_NES) {
         /* kernel shape (crthip_set_shape): small batches take the scanline-parallel encoder */
@@ -1491,7 +1491,7 @@ static void launch_active(crthip_ctx *c, const crthip_params *p, int n, const vo
 #undef CRTHIP_LAUNCH_ACTIVE
 }
 
-/* A sizes call (crthip_fieldpass_sizes / crthip_stills_sizes; c->size_recs): k_active's SZ instantiations, always -- the lane-per-row
+/* A sizes call (crthip_fieldpass_sizes / crthip_stills_sizes; c->call.sizes): k_active's SZ instantiations, always -- the lane-per-row
  * shape whatever crthip_set_shape says (crt_hip.h).  The grid gives every field ceil(desth / 64) whole wavefronts; what the uniform
  * launch decides by p->w is decided by the env's bounds, in ONE launch: the cooperative tiles need every row to hold a 16-byte piece
  * (w_min >= 4), the wide image tile pays where every image fills whole 128-byte lines (w_min >= 1280; CRTHIP_AC_TILE and
@@ -1504,15 +1504,15 @@ static void launch_active_sizes(crthip_ctx *c, const crthip_params *p, int n, co
     const int wrapn = lay.pitch != S::HRES ? lay.wrap : 0;
     ProfScope ps(c, CRTHIP_K_ACTIVE);
     const unsigned char *img = (const unsigned char *) d_images;
-    const size_t extent = ((size_t) c->size_env.extent_hi << 32) | c->size_env.extent_lo;
+    const size_t extent = ((size_t) c->call.size_env.extent_hi << 32) | c->call.size_env.extent_lo;
     const int items = n * ((p->desth + 63) / 64);
     const dim3 block(64);
     const bool noise = p->noise != 0;
-    const bool in4 = p->in_bpp == 4 && c->size_env.w_min >= 4;
+    const bool in4 = p->in_bpp == 4 && c->call.size_env.w_min >= 4;
     const block_order bo = make_block_order(items, c->act_order_env == -1 ? n : c->act_order_env);
     const dim3 ogrid(bo.grid);
-    const bool wide_in = c->ac_tile_env ? c->ac_tile_env == 32 : c->ac_tile ? c->ac_tile == 32 : c->size_env.w_min >= 1280;
-    /* Sizes WITH knob records (crthip_fieldpass_sizes_knobs / crthip_stills_sizes_knobs; c->knob_recs as well): the SZ instantiations
+    const bool wide_in = c->ac_tile_env ? c->ac_tile_env == 32 : c->ac_tile ? c->ac_tile == 32 : c->call.size_env.w_min >= 1280;
+    /* Sizes WITH knob records (crthip_fieldpass_sizes_knobs / crthip_stills_sizes_knobs; c->call.knobs as well): the SZ instantiations
      * with KN (the batch's largest noise is not 0), LV (level records bound) and HU (hue records bound), in the three tile shapes below.
      * The large signal tiles have no such instantiation (compile time: profiles/sizes_knobs_timing.txt) -- such a call takes the
      * 64-byte pieces whatever its wave count, identical bytes.  A combined call that needs none of the three (noise 0 everywhere, nothing
@@ -1521,12 +1521,12 @@ static void launch_active_sizes(crthip_ctx *c, const crthip_params *p, int n, co
     crthip_params plain;
     (void) plain;
     if constexpr (S::CCS == 4) {
-        const bool lv = level_call(c), hu = hue_call(c);
-        if (c->knob_recs && !noise && !lv && !hu) {
+        const bool lv = c->call.levels, hu = c->call.hues;
+        if (c->call.knobs && !noise && !lv && !hu) {
             plain = *p;
-            size_blob_set(&plain, size_blob_knobs_get(p));
+            blob_put_ptr(plain.reserved, size_blob_knobs_get(p));
             p = &plain;                                            /* the plain launches below, with the copy */
-        } else if (c->knob_recs) {
+        } else if (c->call.knobs) {
 #define CRTHIP_LAUNCH_ACTIVE_SZK(I4, AC, KNV, LVV, HUV) \
     hipLaunchKernelGGL((k_active<S, KNV, FAST, I4, true, AC, 16, 16, KNV, LVV, HUV, true>), ogrid, block, 0, c->stream, *p, n, img, extent, dst, lay.fstride, d_state, c->d_jump16, bo.K, bo.per, lay.pitch, lay.shift, wrapn)
 #define CRTHIP_LAUNCH_ACTIVE_SZK_TILE(KNV, LVV, HUV) \
@@ -1578,7 +1578,7 @@ static void launch_margins(crthip_ctx *c, const crthip_params *p, int n, signed 
     const unsigned gap_magic = gap > 0 ? (unsigned) ((0x100000000ull + (unsigned) gap - 1) / (unsigned) gap) : 0u;
     const dim3 grid((per_field + 255) / 256, n < 65535 ? n : 65535);          /* (fields beyond the grid's y limit: the kernel loops) */
     if constexpr (!S::IS_NES && S::CCS == 4) {
-        if (hue_call(c)) {                                       /* (a knob call: its noise is per field, or the batch's largest is 0) */
+        if (c->call.hues) {                                       /* (a knob call: its noise is per field, or the batch's largest is 0) */
             if (p->noise != 0)
                 hipLaunchKernelGGL((k_margin<S, true, true, true>), grid, dim3(256), 0, c->stream,
                                    *p, n, dst, c->fstride, d_state, c->d_jump16, c->d_jump1, c->d_skel, head, gap, tail, gap_magic);
@@ -1588,7 +1588,7 @@ static void launch_margins(crthip_ctx *c, const crthip_params *p, int n, signed 
             return;
         }
     }
-    if (p->noise != 0 && c->knob_recs)
+    if (p->noise != 0 && c->call.knobs)
         hipLaunchKernelGGL((k_margin<S, true, true>), grid, dim3(256), 0, c->stream,
                            *p, n, dst, c->fstride, d_state, c->d_jump16, c->d_jump1, c->d_skel, head, gap, tail, gap_magic);
     else if (p->noise != 0)
@@ -1614,7 +1614,7 @@ static void launch_margins_padded(crthip_ctx *c, const crthip_params *p, int n, 
     const int per_field = p->yo * CF + p->desth * act_per + (S::VRES - p->yo - p->desth) * CF;
     const dim3 grid((per_field + 255) / 256, n < 65535 ? n : 65535);
     if constexpr (!S::IS_NES && S::CCS == 4) {
-        if (hue_call(c)) {
+        if (c->call.hues) {
             if (p->noise != 0)
                 hipLaunchKernelGGL((k_margin_pad<S, true, true, true>), grid, dim3(256), 0, c->stream, *p, n, dst, lay.fstride, lay.shift, d_state,
                                    c->d_jump16, c->d_jump1, c->d_skel, c->fstride, cl, cr, act_magic, lay.wrap);
@@ -1624,7 +1624,7 @@ static void launch_margins_padded(crthip_ctx *c, const crthip_params *p, int n, 
             return;
         }
     }
-    if (p->noise != 0 && c->knob_recs)
+    if (p->noise != 0 && c->call.knobs)
         hipLaunchKernelGGL((k_margin_pad<S, true, true>), grid, dim3(256), 0, c->stream, *p, n, dst, lay.fstride, lay.shift, d_state,
                            c->d_jump16, c->d_jump1, c->d_skel, c->fstride, cl, cr, act_magic, lay.wrap);
     else if (p->noise != 0)
@@ -1721,7 +1721,7 @@ template <class S>
 static void launch_encoder_state(crthip_ctx *c, const crthip_params *p, int n, crthip_state *d_state)
 {
     if constexpr (!S::IS_NES && S::CCS == 4) {
-        if (hue_call(c)) {
+        if (c->call.hues) {
             hipLaunchKernelGGL((k_encoder_state<S, true>), dim3((n + 63) / 64), dim3(64), 0, c->stream, *p, n, d_state);
             return;
         }
@@ -1769,13 +1769,13 @@ int crt_run_encoder_prepare(crthip_ctx *c, const crthip_params *p, bool fused)
          * burst the cached variants were built from serves -- such a call never rebuilds them for their burst; where there are none
          * yet, they are built from the caller's own table (two words of which the blob lends to the records' pointer, crt_dev.h) */
         crthip_params own;
-        if (hue_call(c)) {
+        if (c->call.hues) {
             own = *p;
-            own.burst[0][0] = c->hue_burst0[0];
-            own.burst[0][1] = c->hue_burst0[1];
+            own.burst[0][0] = c->call.burst0[0];
+            own.burst[0][1] = c->call.burst0[1];
             p = &own;
         }
-        const bool burst_same = hue_call(c) || memcmp(c->skel_burst, p->burst, sizeof(p->burst)) == 0;
+        const bool burst_same = c->call.hues || memcmp(c->skel_burst, p->burst, sizeof(p->burst)) == 0;
         const bool need_skel = fused && (!c->skel_valid || !burst_same || c->skel_yo != p->yo || !border_same);
         bool need_nes = false;
         if constexpr (S::IS_NES) need_nes = !c->nes_tab_valid || c->nes_tab_black != p->black_point || c->nes_tab_white != p->white_point;

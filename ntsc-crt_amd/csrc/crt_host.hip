@@ -948,15 +948,154 @@ int crthip_decode(crthip_ctx *c, const crthip_params *p, int n, const signed cha
     return rc;
 }
 
-/* The blob the sync chain of a FUSED launch sees: inp[] was produced here, from a clean analog[] and the encoder, so its
- * sample range is known and the decoder's no-low-cascade envelope can be as wide as that range allows
- * (crthip_params.loskip_wave_max; crt_setup_signal_range).  The stage-level crthip_sync keeps the any-signal bound. */
-static crthip_params with_signal_envelope(const crthip_params *p)
+/* ---- the records of the call in flight (crt_dev.h: rec_call, and the table of the blob words) ----------------------------- */
+
+/* the picture words of an env (crthip_knobs_prepare5; all 0 from crthip_knobs_prepare): do they agree with each other? */
+static bool knobs_env_pic_ok(const crthip_knobs_env *env)
+{
+    if (env->pic == 0) return env->tier_floors == 0 && env->bright_abs_lo == 0;
+    const int lo = env->tier_floors & 0xff, hi = (env->tier_floors >> 8) & 0xff;
+    return env->pic == 1 && (env->tier_floors & ~0xffff) == 0 && lo <= hi && hi <= 3 && lo != 1 && hi != 1 &&
+           env->bright_abs_lo >= 0 && env->bright_abs_lo <= T0_BRIGHT_MAX && (lo < 2 || env->bright_abs_lo == 0);
+}
+
+/* what a crthip_knobs_env must say wherever it arrives: with a call of n fields, or (n == 0) at crthip_seq_bind_knobs */
+static int knobs_env_check(crthip_ctx *c, const crthip_knobs_env *env, int n)
+{
+    if (env->magic != CRTHIP_KNOBS_MAGIC) return set_err(c, CRTHIP_E_ARG, "knobs: env does not come from crthip_knobs_prepare", hipSuccess);
+    if (n && env->n != n) return set_err(c, CRTHIP_E_ARG, "knobs: env was prepared for another number of fields", hipSuccess);
+    if (c->sd.cc_samples == 5)
+        return set_err(c, CRTHIP_E_ARG, "knobs: the 5-sample decoder (PV-1000) takes monitor hue and saturation from the uniform parameters", hipSuccess);
+    if (env->n <= 0 || env->noise_max < 0 || env->sat_abs_max < 0) return set_err(c, CRTHIP_E_ARG, "knobs: env bounds", hipSuccess);
+    if (!knobs_env_pic_ok(env)) return set_err(c, CRTHIP_E_ARG, "knobs: the env's picture words contradict each other (not from crthip_knobs_prepare5)", hipSuccess);
+    return CRTHIP_OK;
+}
+
+/* The one place that writes record pointers into a blob: for a launch that starts at field `first` of the call, every record array
+ * of c->call, advanced to that field, into its words of *q (the table in crt_dev.h).  Sizes: the images have no stride -- the
+ * records' offsets count from the base of the image buffer whatever the launch's first field. */
+static void launch_blob(const crthip_ctx *c, int first, crthip_params *q)
+{
+    const rec_call &k = c->call;
+    if (k.knobs) blob_put_ptr(q->reserved, k.knobs + first);
+    if (k.levels) blob_put_ptr(&q->white, k.levels + first);
+    if (k.hues) blob_put_ptr(&q->burst[0][0], k.hues + first);
+    if (k.sizes) blob_put_ptr(k.knobs ? (void *) &q->col_step_lo : (void *) q->reserved, k.sizes + first);
+}
+
+/* which records a call brings: none (the uniform call), knob records, size records, both, or -- the phases of sequence mode --
+ * whatever crthip_seq_bind_knobs has bound */
+enum { REC_KNOBS = 1, REC_SIZES = 2, REC_SEQ_BOUND = 4 };
+
+/* The one way in.  Checks the records and envs of a call of n fields (p went through check_params), sizes first, and only then
+ * says so in c->call -- a refused call leaves the uniform call standing.  *q = the blob the call's launch code decides by and its
+ * kernels receive: the caller's, with the knob env's bounds where that code reads the uniform values (noise != 0, the encoder's
+ * 24-bit envelope; mon_hue / huesn / huecs / bloom_max_e are read by the KN kernels alone, from the records) and the pointers to the
+ * records of field 0 (launch_blob).  The bindings (crthip_bind_levels / _hues, crthip_seq_bind_knobs) are read here and nowhere else:
+ * every knob call runs with the level and hue records that are bound -- or is refused, before anything is launched.  The host sees
+ * envs, not records: what it checks of the sizes is that the image a wavefront falls back to for a record it refuses
+ * (size_rec_checked, crt_dev.h) lies inside the extent. */
+static int call_begin(crthip_ctx *c, const crthip_params *p, int n, int kinds, const crthip_knob_rec *d_recs, const crthip_knobs_env *env,
+                      const void *d_images, const crthip_size_rec *d_srecs, const crthip_sizes_env *senv, crthip_params *q)
+{
+    rec_call k = {};
+    if (kinds & REC_SEQ_BOUND) {
+        d_recs = c->seq_knob_recs;
+        env = &c->seq_knob_env;
+        if (d_recs) kinds |= REC_KNOBS;                   /* nothing bound: exactly the uniform phase */
+    }
+    *q = *p;
+    if (kinds & REC_SIZES) {
+        if (!d_srecs || !senv) return set_err(c, CRTHIP_E_ARG, "sizes: no records / no env", hipSuccess);
+        if (CHECK_WORD(c, d_srecs)) return CRTHIP_E_ARG;
+        if (senv->magic != CRTHIP_SIZES_MAGIC) return set_err(c, CRTHIP_E_ARG, "sizes: env does not come from crthip_sizes_prepare", hipSuccess);
+        if (senv->n != n) return set_err(c, CRTHIP_E_ARG, "sizes: env was prepared for another number of fields", hipSuccess);
+        if (p->raw != 0) return set_err(c, CRTHIP_E_ARG, "sizes: raw images (the signal rectangle then depends on w and h)", hipSuccess);
+        if (c->system == CRTHIP_SYSTEM_NES) return set_err(c, CRTHIP_E_ARG, "sizes: the NES encoder (PPU pixels) has no per-field instantiation", hipSuccess);
+        if (p->in_bpp == 0) return set_err(c, CRTHIP_E_ARG, "sizes: an input format crt_modulate refuses", hipSuccess);
+        const size_t extent = ((size_t) senv->extent_hi << 32) | senv->extent_lo;
+        const bool spare = (p->flags & CRTHIP_F_IMAGE_SPARE_ROW) != 0;
+        const bool tiles = p->in_bpp == 4 && senv->w_min >= 4;
+        if (senv->w_min < 1 || senv->w_min > senv->w_max || senv->h_min < 1 || senv->h_min > senv->h_max ||
+            extent < (size_t) (tiles ? 4 : 1) * (size_t) p->in_bpp * (spare ? 2 : 1))
+            return set_err(c, CRTHIP_E_ARG, "sizes: the env's bounds contradict each other (not from crthip_sizes_prepare)", hipSuccess);
+        if (d_images && p->in_bpp == 4 && off_grid(d_images, 0, 4))
+            return set_err(c, CRTHIP_E_ARG, "d_images: 4-byte pixels need 4-byte alignment", hipSuccess);
+        k.sizes = d_srecs;
+        k.size_env = *senv;
+    }
+    if (kinds & REC_KNOBS) {
+        if (!d_recs || !env) return CRTHIP_E_ARG;
+        if (CHECK_WORD(c, d_recs)) return CRTHIP_E_ARG;
+        const int rc = knobs_env_check(c, env, n);
+        if (rc) return rc;
+        if ((p->flags & CRTHIP_PHOSPHOR_MASK) == CRTHIP_PHOSPHOR_MASK)
+            return set_err(c, CRTHIP_E_ARG, "phosphor fade and clear at once (crt_main.c:459-463: one or the other)", hipSuccess);
+        if (c->lev_recs) {
+            if (c->lev_env.n != n) return set_err(c, CRTHIP_E_ARG, "levels: the bound crthip_levels_env was prepared for another number of fields", hipSuccess);
+            if (env->pic != 1)
+                return set_err(c, CRTHIP_E_ARG, "levels: bound level records go with the records of crthip_knobs_prepare7 (env->pic == 1: bright per field)", hipSuccess);
+            if (p->flags & CRTHIP_F_NES_BORDER)
+                return set_err(c, CRTHIP_E_ARG, "levels: CRTHIP_F_NES_BORDER bakes the border colour into the cached skeleton with ONE (black point, white point) pair", hipSuccess);
+            if (c->system == CRTHIP_SYSTEM_NES)
+                return set_err(c, CRTHIP_E_ARG, "levels: the NES encoder's samples come from a 512 x 12 table built for ONE (black point, white point) pair", hipSuccess);
+        }
+        if (c->hue_recs) {                                /* likewise, and independently of the levels */
+            if (c->hue_env.n != n) return set_err(c, CRTHIP_E_ARG, "hues: the bound crthip_hues_env was prepared for another number of fields", hipSuccess);
+            if (c->system == CRTHIP_SYSTEM_NES)
+                return set_err(c, CRTHIP_E_ARG, "hues: the NES encoder (PPU pixels) has no per-field instantiation", hipSuccess);
+        }
+        k.knobs = d_recs;
+        k.levels = c->lev_recs;
+        k.lev_env = c->lev_env;
+        k.hues = c->hue_recs;
+        k.burst0[0] = p->burst[0][0];
+        k.burst0[1] = p->burst[0][1];
+        k.pic = env->pic;
+        k.floor_lo = env->pic ? (env->tier_floors & 0xff) : 0;
+        k.loskip = env->loskip_wave_max < LOSKIP_WAVE_MAX ? LOSKIP_WAVE_MAX : env->loskip_wave_max > T0_WAVE_MAX ? T0_WAVE_MAX : env->loskip_wave_max;
+        q->noise = env->noise_max;
+        q->saturation = env->sat_abs_max;
+    }
+    c->call = k;
+    launch_blob(c, 0, q);
+    return CRTHIP_OK;
+}
+
+/* The one way out: c->call is the uniform call again, whichever return leaves the scope (refusals and HIPCHK included) */
+struct CallScope {
+    crthip_ctx *c;
+    explicit CallScope(crthip_ctx *ctx) : c(ctx) {}
+    ~CallScope() { c->call = rec_call{}; }
+};
+
+/* A record entry point: check_params, the way in, body(blob), the way out.  No other line of the library writes c->call. */
+extern "C++" template <class Body>
+int with_records(crthip_ctx *c, const crthip_params *p, int n, int kinds, const crthip_knob_rec *d_recs, const crthip_knobs_env *env,
+                 const void *d_images, const crthip_size_rec *d_srecs, const crthip_sizes_env *senv, Body &&body)
+{
+    int rc = check_params(c, p, n);
+    if (rc) return rc;
+    CallScope scope(c);
+    crthip_params q;
+    rc = call_begin(c, p, n, kinds, d_recs, env, d_images, d_srecs, senv, &q);
+    if (rc) return rc;
+    return body(&q);
+}
+
+/* The blob a sync chain runs on.  Where inp[] was produced here, from a clean analog[] and the encoder, its sample range is known and
+ * the decoder's no-low-cascade envelope can be as wide as that range allows (crthip_params.loskip_wave_max; crt_setup_signal_range)
+ * -- with knob records, as wide as it is at the call's widest noise (crthip_knobs_prepare).  A signal that is not encoder-made (and
+ * the stage-level crthip_sync) keeps the caller's any-signal bound. */
+static crthip_params sync_blob(const crthip_ctx *c, const crthip_params *p, bool encoder_made)
 {
     crthip_params q = *p;
-    int lo, hi;
-    crt_setup_signal_range(p, &lo, &hi);
-    q.loskip_wave_max = crt_setup_loskip_bound(lo, hi);
+    if (encoder_made && c->call.knobs) q.loskip_wave_max = c->call.loskip;
+    else if (encoder_made) {
+        int lo, hi;
+        crt_setup_signal_range(p, &lo, &hi);
+        q.loskip_wave_max = crt_setup_loskip_bound(lo, hi);
+    }
     return q;
 }
 
@@ -975,23 +1114,9 @@ static int fieldpass_chunk(crthip_ctx *c, const crthip_params *p, int enc, int f
     crthip_line *ln = c->d_lines + (size_t) first * c->sd.lines;
     int rc = CRTHIP_OK;
     bool preset = false;
-    /* per-field knobs: the blob of this chunk's launches points at the record of ITS first field (crt_dev.h, knob_blob_set) */
-    crthip_params pk;
-    if (c->knob_recs) {
-        pk = *p;
-        knob_blob_set(&pk, c->knob_recs + first);
-        if (level_call(c)) level_blob_set(&pk, level_blob_get(p) + first);
-        if (hue_call(c)) hue_blob_set(&pk, hue_blob_get(p) + first);
-        /* ... and with mixed sizes as well (crthip_fieldpass_sizes_knobs): the size records' pointer, in its home of such a call */
-        if (c->size_recs) size_blob_knobs_set(&pk, c->size_recs + first);
-        p = &pk;
-    } else if (c->size_recs) {
-        /* mixed sizes: likewise the size record of the chunk's first field; the images have no stride (istride == 0: img stays the
-         * base the records' offsets count from) */
-        pk = *p;
-        size_blob_set(&pk, c->size_recs + first);
-        p = &pk;
-    }
+    crthip_params pk = *p;
+    launch_blob(c, first, &pk);                           /* the records of THIS chunk's first field */
+    p = &pk;
     if (part & 1) {
         const bool vhs_rand = c->system == CRTHIP_SYSTEM_NTSCVHS && !(p->flags & CRTHIP_F_VHS_LCG_NOISE);
         if (vhs_rand || (p->flags & CRTHIP_F_NO_VSYNC)) {
@@ -1023,7 +1148,7 @@ static int fieldpass_chunk(crthip_ctx *c, const crthip_params *p, int enc, int f
                  * leaves in the state (ccf preset, M6) is applied by the sync chain's own waves when it follows at once
                  * (k_hsync_wave, preset_ccf): one launch less per field-pass */
                 preset = (part & 4) && p->out_bpp != 0 && c->system != CRTHIP_SYSTEM_NTSCVHS;   /* (VHS also resets hsync there) */
-                if (hue_call(c)) preset = false;      /* the preset comes from every field's own burst table: k_encoder_state's HU instantiation */
+                if (c->call.hues) preset = false;     /* the preset comes from every field's own burst table: k_encoder_state's HU instantiation */
                 rc = crt_run_encoder(c, p, n, img, istride, inp, st, true, 1, !preset, &lay);
             } else {
                 /* invalid input format: crt_modulate is a no-op, the decoder sees a clean field + noise
@@ -1035,8 +1160,7 @@ static int fieldpass_chunk(crthip_ctx *c, const crthip_params *p, int enc, int f
         if (rc) return rc;
     }
     if ((part & 4) && p->out_bpp != 0) {
-        crthip_params q = enc == 0 && !c->knob_recs ? with_signal_envelope(p) : *p;
-        if (enc == 0 && c->knob_recs) q.loskip_wave_max = c->knob_loskip;      /* the envelope at the batch's widest noise (crthip_knobs_prepare) */
+        const crthip_params q = sync_blob(c, p, enc == 0);
         rc = crt_run_sync(c, &q, n, inp, st, ln, 1, preset ? 1 : 0, &lay);
         if (rc) return rc;
     }
@@ -1047,48 +1171,57 @@ static int fieldpass_chunk(crthip_ctx *c, const crthip_params *p, int enc, int f
     return rc;
 }
 
-/* crthip_fieldpass, and crthip_fieldpass_knobs when c->knob_recs is set (p is then the library's copy carrying the batch's bounds) */
+/* Room for n fields in the workspace, no claim on the signal it holds -- what crthip_fieldpass_signal may unpad is the signal of the
+ * last call that was enqueued COMPLETELY, and a call refused half-way leaves none --, and (tables) the encoder's tables for p, (re)built
+ * on the caller's stream before anything forks */
+static int encoder_ready(crthip_ctx *c, const crthip_params *p, int n, bool tables)
+{
+    if (n > c->cap_fields) {
+        const int rc = crthip_reserve(c, n);
+        if (rc) return rc;
+    }
+    c->last_n = 0;
+    return tables ? crt_run_encoder_prepare(c, p, true) : CRTHIP_OK;
+}
+
+/* What crthip_fieldpass* and crthip_stills* do with their arguments before the first launch (p went through check_params): the buffer
+ * contract (null_msg: what the error string says of a null pointer, nullptr = nothing), the encoder's (*enc: 0 = encodes, 1 = an
+ * input format crt_modulate refuses), the workspace and the tables, and *lay = the signal between the call's encoder and its decoder:
+ * padded lines where the fused LCG-noise encoder writes it (crt_dev.h) */
+static int fused_front(crthip_ctx *c, const crthip_params *p, int n, const void *d_images, size_t istride, void *d_out, size_t ostride,
+                       crthip_state *d_state, const char *null_msg, int *enc, sig_layout *lay)
+{
+    int rc;
+    if (!d_images || !d_out || !d_state) return null_msg ? set_err(c, CRTHIP_E_ARG, null_msg, hipSuccess) : CRTHIP_E_ARG;
+    if ((rc = check_images(c, p, d_images, istride)) || (rc = check_out(c, p, d_out, ostride)) || (rc = CHECK_WORD(c, d_state))) return rc;
+    const bool vhs_rand = c->system == CRTHIP_SYSTEM_NTSCVHS && !(p->flags & CRTHIP_F_VHS_LCG_NOISE);
+    if (vhs_rand && !c->d_vhs_hist)
+        return set_err(c, CRTHIP_E_ARG, "VHS: no generator histories bound (crthip_vhs_bind_history)", hipSuccess);
+    *enc = check_encoder(c, p);
+    if (*enc < 0) return *enc;
+    HIPCHK(c, hipSetDevice(c->device));
+    rc = encoder_ready(c, p, n, *enc == 0);
+    if (rc) return rc;
+    if (*enc != 0 || vhs_rand || !crt_fused_layout(c, p, n, lay)) *lay = flat_layout(c);
+    return CRTHIP_OK;
+}
+
+/* every crthip_fieldpass* entry point, on the blob of its records (call_begin) */
 static int fieldpass_body(crthip_ctx *c, const crthip_params *p, int n, const void *d_images, size_t istride,
                           void *d_out, size_t ostride, crthip_state *d_state)
 {
-    int rc = check_params(c, p, n);
-    if (rc) return rc;
-    if (!d_images || !d_out || !d_state) return CRTHIP_E_ARG;
-    if ((rc = check_images(c, p, d_images, istride)) || (rc = check_out(c, p, d_out, ostride)) || (rc = CHECK_WORD(c, d_state))) return rc;
-    if (c->system == CRTHIP_SYSTEM_NTSCVHS && !(p->flags & CRTHIP_F_VHS_LCG_NOISE) && !c->d_vhs_hist)
-        return set_err(c, CRTHIP_E_ARG, "VHS: no generator histories bound (crthip_vhs_bind_history)", hipSuccess);
-    int enc = check_encoder(c, p);
-    if (enc < 0) return enc;
-    HIPCHK(c, hipSetDevice(c->device));
-    if (n > c->cap_fields) {
-        rc = crthip_reserve(c, n);
-        if (rc) return rc;
-    }
-    /* Fields are independent, so a large batch is cut into chunks that alternate between the
-     * caller's stream and an internal one: the latency-bound kernels of one chunk (sync chain,
-     * margins, launch gaps) then overlap the VALU-bound kernels of the other.  The internal stream
-     * is fenced by events on both sides, so to the caller everything is still ordered on ITS stream. */
-    if (enc == 0) {
-        /* tables shared by all chunks are (re)built here, on the caller's stream, before any fork */
-        rc = crt_run_encoder_prepare(c, p, true);
-        if (rc) return rc;
-    }
-    /* the signal between this call's encoder and decoder: padded lines where the fused LCG-noise encoder writes it (crt_dev.h) */
+    int enc;
     sig_layout lay;
-    const bool vhs_rand_path = c->system == CRTHIP_SYSTEM_NTSCVHS && !(p->flags & CRTHIP_F_VHS_LCG_NOISE);
-    if (enc != 0 || vhs_rand_path || !crt_fused_layout(c, p, n, &lay)) lay = flat_layout(c);
-    /* what crthip_fieldpass_signal may unpad is the signal of the last pass that was enqueued COMPLETELY: a pass refused half-way
-     * (the decoder's argument checks come after the encoder and the sync chain) leaves no claim on the workspace */
-    c->last_n = 0;
-    /* 0 = automatic.  The idea: run the vector / latency bound encoder + sync chain of one chunk under the HBM-write
-     * bound decoder of the previous one.  Measured on MI355X (profiles/r02_overlap_sweep.txt): at 1080p the encoder's
-     * image reads and the decoder's picture writes already saturate what HBM delivers for this access mix, running
-     * them side by side is slower than one after the other (2 chunks -3 %, 8 chunks -19 %); at 640x480 every kernel is
-     * vector bound and chunks only add latency.  So automatic means: one chunk. */
-    int want_chunks = c->overlap_chunks;
-    if (want_chunks == 0) want_chunks = 1;       /* measured: no configuration gains (profiles/r02_overlap_sweep.txt); round 3 also
-                                                    tried only the sync chain of the second half of the batch under the decoder
-                                                    of the first: 3-4 % slower at 640x480 and 1080p alike (profiles/r03_1080p_experiments.txt) */
+    int rc = fused_front(c, p, n, d_images, istride, d_out, ostride, d_state, nullptr, &enc, &lay);
+    if (rc) return rc;
+    /* Fields are independent, so a large batch can be cut into chunks (crthip_set_overlap) -- the idea: run the vector / latency bound
+     * encoder + sync chain of one chunk under the HBM-write bound decoder of the previous one.  0 = automatic = one chunk: no
+     * configuration gains.  Measured on MI355X (profiles/r02_overlap_sweep.txt): at 1080p the encoder's image reads and the decoder's
+     * picture writes already saturate what HBM delivers for this access mix, running them side by side is slower than one after the
+     * other (2 chunks -3 %, 8 chunks -19 %); at 640x480 every kernel is vector bound and chunks only add latency.  Round 3 also tried
+     * only the sync chain of the second half of the batch under the decoder of the first: 3-4 % slower at 640x480 and 1080p alike
+     * (profiles/r03_1080p_experiments.txt). */
+    const int want_chunks = c->overlap_chunks ? c->overlap_chunks : 1;
     const int nchunks = (want_chunks > 1 && n >= 256 * want_chunks && !c->prof) ? want_chunks : 1;
     if (nchunks == 1) {
         rc = fieldpass_chunk(c, p, enc, 0, n, 7, lay, d_images, istride, d_out, ostride, d_state);
@@ -1129,174 +1262,31 @@ static int fieldpass_body(crthip_ctx *c, const crthip_params *p, int n, const vo
 int crthip_fieldpass(crthip_ctx *c, const crthip_params *p, int n, const void *d_images, size_t istride,
                      void *d_out, size_t ostride, crthip_state *d_state)
 {
-    if (c) { c->knob_recs = nullptr; c->size_recs = nullptr; }
-    return fieldpass_body(c, p, n, d_images, istride, d_out, ostride, d_state);
-}
-
-/* What every per-field-knob entry point checks (p went through check_params), and *q = the blob its launch code decides by: the
- * call's bounds where that code reads the uniform values (noise != 0, the encoder's 24-bit envelope), the device pointer to the
- * record of the call's field 0 (knob_blob_set) for the KN kernels -- mon_hue / huesn / huecs / bloom_max_e are read by them alone,
- * from the records -- and c->knob_loskip = the sync chain's no-low-cascade bound.  The caller sets c->knob_recs for the duration of
- * its launches and clears it on every way out. */
-/* the picture words of an env (crthip_knobs_prepare5; all 0 from crthip_knobs_prepare): do they agree with each other? */
-static bool knobs_env_pic_ok(const crthip_knobs_env *env)
-{
-    if (env->pic == 0) return env->tier_floors == 0 && env->bright_abs_lo == 0;
-    const int lo = env->tier_floors & 0xff, hi = (env->tier_floors >> 8) & 0xff;
-    return env->pic == 1 && (env->tier_floors & ~0xffff) == 0 && lo <= hi && hi <= 3 && lo != 1 && hi != 1 &&
-           env->bright_abs_lo >= 0 && env->bright_abs_lo <= T0_BRIGHT_MAX && (lo < 2 || env->bright_abs_lo == 0);
-}
-
-static int knobs_blob(crthip_ctx *c, const crthip_params *p, int n, const crthip_knob_rec *d_recs, const crthip_knobs_env *env, crthip_params *q)
-{
-    c->lev_on = 0;
-    c->hue_on = 0;
-    if (!d_recs || !env) return CRTHIP_E_ARG;
-    if (CHECK_WORD(c, d_recs)) return CRTHIP_E_ARG;
-    if (env->magic != CRTHIP_KNOBS_MAGIC) return set_err(c, CRTHIP_E_ARG, "knobs: env does not come from crthip_knobs_prepare", hipSuccess);
-    if (env->n != n) return set_err(c, CRTHIP_E_ARG, "knobs: env was prepared for another number of fields", hipSuccess);
-    if ((p->flags & CRTHIP_PHOSPHOR_MASK) == CRTHIP_PHOSPHOR_MASK)
-        return set_err(c, CRTHIP_E_ARG, "phosphor fade and clear at once (crt_main.c:459-463: one or the other)", hipSuccess);
-    if (c->sd.cc_samples == 5)
-        return set_err(c, CRTHIP_E_ARG, "knobs: the 5-sample decoder (PV-1000) takes monitor hue and saturation from the uniform parameters", hipSuccess);
-    if (env->noise_max < 0 || env->sat_abs_max < 0) return set_err(c, CRTHIP_E_ARG, "knobs: env bounds", hipSuccess);
-    if (!knobs_env_pic_ok(env)) return set_err(c, CRTHIP_E_ARG, "knobs: the env's picture words contradict each other (not from crthip_knobs_prepare5)", hipSuccess);
-    /* level records bound (crthip_bind_levels): every knob call runs with them -- or is refused here, before anything is launched */
-    if (c->lev_recs) {
-        if (c->lev_env.n != n) return set_err(c, CRTHIP_E_ARG, "levels: the bound crthip_levels_env was prepared for another number of fields", hipSuccess);
-        if (env->pic != 1)
-            return set_err(c, CRTHIP_E_ARG, "levels: bound level records go with the records of crthip_knobs_prepare7 (env->pic == 1: bright per field)", hipSuccess);
-        if (p->flags & CRTHIP_F_NES_BORDER)
-            return set_err(c, CRTHIP_E_ARG, "levels: CRTHIP_F_NES_BORDER bakes the border colour into the cached skeleton with ONE (black point, white point) pair", hipSuccess);
-        if (c->system == CRTHIP_SYSTEM_NES)
-            return set_err(c, CRTHIP_E_ARG, "levels: the NES encoder's samples come from a 512 x 12 table built for ONE (black point, white point) pair", hipSuccess);
-    }
-    /* hue records bound (crthip_bind_hues): likewise, and independently of the levels */
-    if (c->hue_recs) {
-        if (c->hue_env.n != n) return set_err(c, CRTHIP_E_ARG, "hues: the bound crthip_hues_env was prepared for another number of fields", hipSuccess);
-        if (c->system == CRTHIP_SYSTEM_NES)
-            return set_err(c, CRTHIP_E_ARG, "hues: the NES encoder (PPU pixels) has no per-field instantiation", hipSuccess);
-    }
-    c->knob_pic = env->pic;
-    c->knob_floor_lo = env->pic ? (env->tier_floors & 0xff) : 0;
-    *q = *p;
-    q->noise = env->noise_max;
-    q->saturation = env->sat_abs_max;
-    knob_blob_set(q, d_recs);
-    if (c->lev_recs) {
-        /* the LV kernels read white / ire_base from the records; the blob's two words carry the pointer to them (crt_dev.h), and
-         * the launch code decides by c->lev_env where it read them (encoder_fast_ok) */
-        level_blob_set(q, c->lev_recs);
-        c->lev_on = 1;
-    }
-    if (c->hue_recs) {
-        /* the HU kernels read burst / modI / modQ from the records; two words of the blob's burst table carry the pointer to them
-         * (crt_dev.h), the caller's own two are kept for the skeleton cache (crt_run_encoder_prepare) */
-        c->hue_burst0[0] = p->burst[0][0];
-        c->hue_burst0[1] = p->burst[0][1];
-        hue_blob_set(q, c->hue_recs);
-        c->hue_on = 1;
-    }
-    c->knob_loskip = env->loskip_wave_max < LOSKIP_WAVE_MAX ? LOSKIP_WAVE_MAX : env->loskip_wave_max > T0_WAVE_MAX ? T0_WAVE_MAX : env->loskip_wave_max;
-    return CRTHIP_OK;
+    return with_records(c, p, n, 0, nullptr, nullptr, nullptr, nullptr, nullptr, [&](const crthip_params *q) {
+        return fieldpass_body(c, q, n, d_images, istride, d_out, ostride, d_state); });
 }
 
 int crthip_fieldpass_knobs(crthip_ctx *c, const crthip_params *p, int n, const void *d_images, size_t istride,
                            void *d_out, size_t ostride, crthip_state *d_state, const crthip_knob_rec *d_recs, const crthip_knobs_env *env)
 {
-    int rc = check_params(c, p, n);
-    if (rc) return rc;
-    crthip_params q;
-    rc = knobs_blob(c, p, n, d_recs, env, &q);
-    if (rc) return rc;
-    c->knob_recs = d_recs;
-    c->size_recs = nullptr;
-    rc = fieldpass_body(c, &q, n, d_images, istride, d_out, ostride, d_state);
-    c->knob_recs = nullptr;
-    return rc;
+    return with_records(c, p, n, REC_KNOBS, d_recs, env, nullptr, nullptr, nullptr, [&](const crthip_params *q) {
+        return fieldpass_body(c, q, n, d_images, istride, d_out, ostride, d_state); });
 }
 
-/* What both sizes entry points check (p went through check_params), and *q = the blob their launches carry: the device pointer to
- * the size record of the call's field 0 in `reserved` (size_blob_set; fieldpass_chunk moves it to its chunk's first field).  The
- * caller sets c->size_recs for the duration of its launches and clears it on every way out; c->size_env = the bounds the encoder's
- * launch code decides by where the uniform call reads p->w.  The host sees the env, not the records: what it checks here is that the
- * image a wavefront falls back to for a record it refuses (size_rec_checked, crt_dev.h) lies inside the extent. */
-static int sizes_blob(crthip_ctx *c, const crthip_params *p, int n, const void *d_images, const crthip_size_rec *d_srecs,
-                      const crthip_sizes_env *senv, crthip_params *q)
-{
-    if (!d_srecs || !senv) return set_err(c, CRTHIP_E_ARG, "sizes: no records / no env", hipSuccess);
-    if (CHECK_WORD(c, d_srecs)) return CRTHIP_E_ARG;
-    if (senv->magic != CRTHIP_SIZES_MAGIC) return set_err(c, CRTHIP_E_ARG, "sizes: env does not come from crthip_sizes_prepare", hipSuccess);
-    if (senv->n != n) return set_err(c, CRTHIP_E_ARG, "sizes: env was prepared for another number of fields", hipSuccess);
-    if (p->raw != 0) return set_err(c, CRTHIP_E_ARG, "sizes: raw images (the signal rectangle then depends on w and h)", hipSuccess);
-    if (c->system == CRTHIP_SYSTEM_NES) return set_err(c, CRTHIP_E_ARG, "sizes: the NES encoder (PPU pixels) has no per-field instantiation", hipSuccess);
-    if (p->in_bpp == 0) return set_err(c, CRTHIP_E_ARG, "sizes: an input format crt_modulate refuses", hipSuccess);
-    const size_t extent = ((size_t) senv->extent_hi << 32) | senv->extent_lo;
-    const bool spare = (p->flags & CRTHIP_F_IMAGE_SPARE_ROW) != 0;
-    const bool tiles = p->in_bpp == 4 && senv->w_min >= 4;
-    if (senv->w_min < 1 || senv->w_min > senv->w_max || senv->h_min < 1 || senv->h_min > senv->h_max ||
-        extent < (size_t) (tiles ? 4 : 1) * (size_t) p->in_bpp * (spare ? 2 : 1))
-        return set_err(c, CRTHIP_E_ARG, "sizes: the env's bounds contradict each other (not from crthip_sizes_prepare)", hipSuccess);
-    if (d_images && p->in_bpp == 4 && off_grid(d_images, 0, 4))
-        return set_err(c, CRTHIP_E_ARG, "d_images: 4-byte pixels need 4-byte alignment", hipSuccess);
-    *q = *p;
-    size_blob_set(q, d_srecs);
-    c->size_env = *senv;
-    return CRTHIP_OK;
-}
-
+/* (a call with size records has no image stride: `istride` carries the extent of the image buffer to the SZ kernels, crt_encode.hip) */
 int crthip_fieldpass_sizes(crthip_ctx *c, const crthip_params *p, int n, const void *d_images, void *d_out, size_t ostride,
                            crthip_state *d_state, const crthip_size_rec *d_srecs, const crthip_sizes_env *senv)
 {
-    int rc = check_params(c, p, n);
-    if (rc) return rc;
-    crthip_params q;
-    rc = sizes_blob(c, p, n, d_images, d_srecs, senv, &q);
-    if (rc) return rc;
-    c->knob_recs = nullptr;
-    c->size_recs = d_srecs;
-    rc = fieldpass_body(c, &q, n, d_images, 0, d_out, ostride, d_state);
-    c->size_recs = nullptr;
-    return rc;
-}
-
-/* Sizes AND knob records: what both parents check, in their own words, and *q = the knob call's blob (knobs_blob: the bounds, the
- * knob / level / hue pointers) with the size records' pointer in its home of such a call (size_blob_knobs_set, crt_dev.h).  The
- * caller sets c->knob_recs and c->size_recs for the duration of its launches; sizes_knobs_done clears everything on every way out. */
-static int sizes_knobs_blob(crthip_ctx *c, const crthip_params *p, int n, const void *d_images, const crthip_size_rec *d_srecs,
-                            const crthip_sizes_env *senv, const crthip_knob_rec *d_recs, const crthip_knobs_env *env, crthip_params *q)
-{
-    crthip_params qs;
-    int rc = sizes_blob(c, p, n, d_images, d_srecs, senv, &qs);
-    if (rc) return rc;
-    rc = knobs_blob(c, p, n, d_recs, env, q);
-    if (rc) return rc;
-    size_blob_knobs_set(q, d_srecs);
-    return CRTHIP_OK;
-}
-static int sizes_knobs_done(crthip_ctx *c, int rc)
-{
-    c->knob_recs = nullptr;
-    c->size_recs = nullptr;
-    c->lev_on = 0;
-    c->hue_on = 0;
-    return rc;
+    return with_records(c, p, n, REC_SIZES, nullptr, nullptr, d_images, d_srecs, senv, [&](const crthip_params *q) {
+        return fieldpass_body(c, q, n, d_images, 0, d_out, ostride, d_state); });
 }
 
 int crthip_fieldpass_sizes_knobs(crthip_ctx *c, const crthip_params *p, int n, const void *d_images, void *d_out, size_t ostride,
                                  crthip_state *d_state, const crthip_size_rec *d_srecs, const crthip_sizes_env *senv,
                                  const crthip_knob_rec *d_recs, const crthip_knobs_env *env)
 {
-    int rc = check_params(c, p, n);
-    if (rc) return rc;
-    c->knob_recs = nullptr;
-    c->size_recs = nullptr;
-    crthip_params q;
-    rc = sizes_knobs_blob(c, p, n, d_images, d_srecs, senv, d_recs, env, &q);
-    if (rc) return sizes_knobs_done(c, rc);
-    c->knob_recs = d_recs;
-    c->size_recs = d_srecs;
-    return sizes_knobs_done(c, fieldpass_body(c, &q, n, d_images, 0, d_out, ostride, d_state));
+    return with_records(c, p, n, REC_SIZES | REC_KNOBS, d_recs, env, d_images, d_srecs, senv, [&](const crthip_params *q) {
+        return fieldpass_body(c, q, n, d_images, 0, d_out, ostride, d_state); });
 }
 
 /* ---- stills ---------------------------------------------------------------------------------------------------------------- */
@@ -1341,41 +1331,22 @@ int crthip_stills_reserve(crthip_ctx *c, int n, int n_distinct)
     return stills_workspace(c, (size_t) n * n_distinct, 0);
 }
 
-/* crthip_stills, and crthip_stills_knobs when c->knob_recs is set (p is then the library's copy carrying the batch's bounds: p->noise
- * = the call's largest noise, which decides the shared path) */
+/* every crthip_stills* entry point, on the blob of its records (call_begin: with knob records p->noise = the call's largest noise,
+ * which decides the shared path) */
 static int stills_body(crthip_ctx *c, const crthip_params *p, int n, const void *d_images, size_t istride,
                        void *d_out, size_t ostride, crthip_state *d_state, int n_passes, const crthip_pass *sched)
 {
-    int rc = check_params(c, p, n);
-    if (rc) return rc;
     if (n_passes <= 0 || n_passes > CRTHIP_STILLS_MAX_PASSES)
         return set_err(c, CRTHIP_E_ARG, "crthip_stills: n_passes must be 1 .. CRTHIP_STILLS_MAX_PASSES", hipSuccess);
     if (!sched) return set_err(c, CRTHIP_E_ARG, "crthip_stills: no schedule (sched == NULL)", hipSuccess);
-    if (!d_images || !d_out || !d_state) return set_err(c, CRTHIP_E_ARG, "crthip_stills: null device pointer", hipSuccess);
-    if ((rc = check_images(c, p, d_images, istride)) || (rc = check_out(c, p, d_out, ostride)) || (rc = CHECK_WORD(c, d_state))) return rc;
-    const bool vhs_rand = c->system == CRTHIP_SYSTEM_NTSCVHS && !(p->flags & CRTHIP_F_VHS_LCG_NOISE);
-    if (vhs_rand && !c->d_vhs_hist)
-        return set_err(c, CRTHIP_E_ARG, "VHS: no generator histories bound (crthip_vhs_bind_history)", hipSuccess);
-    const int enc = check_encoder(c, p);
-    if (enc < 0) return enc;
-    if (p->out_bpp != 0) {
-        /* what the decoder of pass 0 would refuse, before anything runs */
-        rc = crt_decode_check(c, p);
-        if (rc) return rc;
-    }
-    HIPCHK(c, hipSetDevice(c->device));
-    if (n > c->cap_fields) {
-        rc = crthip_reserve(c, n);
-        if (rc) return rc;
-    }
-    if (enc == 0) {
-        rc = crt_run_encoder_prepare(c, p, true);
-        if (rc) return rc;
-    }
-    /* the layout a field-pass of these n fields takes (crthip_fieldpass) */
+    int rc;
+    if (p->out_bpp != 0 && (rc = crt_decode_check(c, p))) return rc;      /* what the decoder of pass 0 would refuse, before anything runs */
+    /* the rest as a field-pass of these n fields, its layout included; crthip_fieldpass_signal is refused after a stills call (crt_hip.h) */
+    int enc;
     sig_layout lay;
-    if (enc != 0 || vhs_rand || !crt_fused_layout(c, p, n, &lay)) lay = flat_layout(c);
-    c->last_n = 0;                                        /* crthip_fieldpass_signal: refused after a stills call (crt_hip.h) */
+    rc = fused_front(c, p, n, d_images, istride, d_out, ostride, d_state, "crthip_stills: null device pointer", &enc, &lay);
+    if (rc) return rc;
+    const bool vhs_rand = c->system == CRTHIP_SYSTEM_NTSCVHS && !(p->flags & CRTHIP_F_VHS_LCG_NOISE);
     const dim3 gn((n + 63) / 64), b64(64);
     const bool shared = p->noise == 0 && enc == 0 && !vhs_rand && !(p->flags & CRTHIP_F_NO_VSYNC) && p->out_bpp != 0;
     if (!shared) {
@@ -1414,9 +1385,8 @@ static int stills_body(crthip_ctx *c, const crthip_params *p, int n, const void 
     /* what crt_modulate leaves in the state is applied per pass: by the sync chain's own waves (preset_ccf), or -- VHS, which also
      * resets hsync there -- by k_encoder_state, exactly as a field-pass does */
     /* (hue records: the preset comes from every still's own burst table, k_encoder_state's HU instantiation, as in a field-pass) */
-    const bool preset = c->system != CRTHIP_SYSTEM_NTSCVHS && !hue_call(c);
-    crthip_params q = c->knob_recs ? *p : with_signal_envelope(p);
-    if (c->knob_recs) q.loskip_wave_max = c->knob_loskip;     /* the envelope at the batch's widest noise (crthip_knobs_prepare) */
+    const bool preset = c->system != CRTHIP_SYSTEM_NTSCVHS && !c->call.hues;
+    const crthip_params q = sync_blob(c, p, true);
     unsigned char *out = (unsigned char *) d_out;
     for (int r = 0; r < n_passes; r++) {
         const signed char *sig = c->d_still_sig + (size_t) slot[r] * slot_bytes;
@@ -1438,64 +1408,37 @@ static int stills_body(crthip_ctx *c, const crthip_params *p, int n, const void 
 int crthip_stills(crthip_ctx *c, const crthip_params *p, int n, const void *d_images, size_t istride,
                   void *d_out, size_t ostride, crthip_state *d_state, int n_passes, const crthip_pass *sched)
 {
-    if (c) { c->knob_recs = nullptr; c->size_recs = nullptr; }
-    return stills_body(c, p, n, d_images, istride, d_out, ostride, d_state, n_passes, sched);
+    return with_records(c, p, n, 0, nullptr, nullptr, nullptr, nullptr, nullptr, [&](const crthip_params *q) {
+        return stills_body(c, q, n, d_images, istride, d_out, ostride, d_state, n_passes, sched); });
 }
 
-/* record k is still k's look in every pass: every launch of the body reads the records the way a field-pass of the n stills does.
- * With the call's largest noise 0 the clean signal of every distinct entry is encoded once WITH the blob of the records (the LV / HU
- * instantiations where levels / hues are bound: a still's clean signal depends on its own levels and hue, not on the pass). */
+/* Record k is still k's look and / or size in every pass: every launch of the body reads the records the way a field-pass of the n
+ * stills does.  With the call's largest noise 0 the clean signal of every distinct entry is encoded once WITH the blob of the records
+ * (the SZ instantiations, with LV / HU where levels / hues are bound: a still's clean signal depends on its own size, levels and hue,
+ * not on the pass). */
 int crthip_stills_knobs(crthip_ctx *c, const crthip_params *p, int n, const void *d_images, size_t istride,
                         void *d_out, size_t ostride, crthip_state *d_state, int n_passes, const crthip_pass *sched,
                         const crthip_knob_rec *d_recs, const crthip_knobs_env *env)
 {
-    int rc = check_params(c, p, n);
-    if (rc) return rc;
-    crthip_params q;
-    rc = knobs_blob(c, p, n, d_recs, env, &q);
-    if (rc) return rc;
-    c->knob_recs = d_recs;
-    c->size_recs = nullptr;
-    rc = stills_body(c, &q, n, d_images, istride, d_out, ostride, d_state, n_passes, sched);
-    c->knob_recs = nullptr;
-    return rc;
+    return with_records(c, p, n, REC_KNOBS, d_recs, env, nullptr, nullptr, nullptr, [&](const crthip_params *q) {
+        return stills_body(c, q, n, d_images, istride, d_out, ostride, d_state, n_passes, sched); });
 }
 
-/* record k is still k's size in every pass; at noise 0 every distinct entry is encoded once with the records' blob (a still's clean
- * signal depends on its own size, not on the pass) */
 int crthip_stills_sizes(crthip_ctx *c, const crthip_params *p, int n, const void *d_images, void *d_out, size_t ostride,
                         crthip_state *d_state, int n_passes, const crthip_pass *sched,
                         const crthip_size_rec *d_srecs, const crthip_sizes_env *senv)
 {
-    int rc = check_params(c, p, n);
-    if (rc) return rc;
-    crthip_params q;
-    rc = sizes_blob(c, p, n, d_images, d_srecs, senv, &q);
-    if (rc) return rc;
-    c->knob_recs = nullptr;
-    c->size_recs = d_srecs;
-    rc = stills_body(c, &q, n, d_images, 0, d_out, ostride, d_state, n_passes, sched);
-    c->size_recs = nullptr;
-    return rc;
+    return with_records(c, p, n, REC_SIZES, nullptr, nullptr, d_images, d_srecs, senv, [&](const crthip_params *q) {
+        return stills_body(c, q, n, d_images, 0, d_out, ostride, d_state, n_passes, sched); });
 }
 
-/* records k are still k's size AND look in every pass; with the call's largest noise 0 every distinct entry is encoded once with the
- * blob of all the records (the SZ + LV / HU instantiations: a still's clean signal depends on its own size, levels and hue) */
 int crthip_stills_sizes_knobs(crthip_ctx *c, const crthip_params *p, int n, const void *d_images, void *d_out, size_t ostride,
                               crthip_state *d_state, int n_passes, const crthip_pass *sched,
                               const crthip_size_rec *d_srecs, const crthip_sizes_env *senv,
                               const crthip_knob_rec *d_recs, const crthip_knobs_env *env)
 {
-    int rc = check_params(c, p, n);
-    if (rc) return rc;
-    c->knob_recs = nullptr;
-    c->size_recs = nullptr;
-    crthip_params q;
-    rc = sizes_knobs_blob(c, p, n, d_images, d_srecs, senv, d_recs, env, &q);
-    if (rc) return sizes_knobs_done(c, rc);
-    c->knob_recs = d_recs;
-    c->size_recs = d_srecs;
-    return sizes_knobs_done(c, stills_body(c, &q, n, d_images, 0, d_out, ostride, d_state, n_passes, sched));
+    return with_records(c, p, n, REC_SIZES | REC_KNOBS, d_recs, env, d_images, d_srecs, senv, [&](const crthip_params *q) {
+        return stills_body(c, q, n, d_images, 0, d_out, ostride, d_state, n_passes, sched); });
 }
 
 unsigned crthip_table_generation(const crthip_ctx *c) { return c ? c->table_gen : 0u; }
@@ -1627,15 +1570,12 @@ static void seq_record_layout(crthip_ctx *c, int n) { c->last_lay = flat_layout(
  * caller's kernel that gives every field its initial pair -- the previous field's pair of sc.guess, or the incoming pair of its
  * set --, then the ccf preset (crt_ntsc.c:325-329), the sync chain, and k_seq_compare (guess <- finals, one flag for all fields).
  * After pass j the first j fields of every set are final, so more than `limit` = longest set + 1 passes cannot happen; `stuck` is
- * what the caller says if it does (say so instead of returning a half-converged chain).  The blob the chain runs on: the
- * envelope of a signal produced here (with_signal_envelope), or with records the envelope at their widest noise
- * (crthip_knobs_prepare). */
+ * what the caller says if it does (say so instead of returning a half-converged chain). */
 extern "C++" template <class Load>
 int seq_converge(crthip_ctx *c, const crthip_params *p, int n, crthip_state *d_state, const SetsScratch &sc, int limit,
                  const char *stuck, int *passes_out, Load &&load)
 {
-    crthip_params q = c->knob_recs ? *p : with_signal_envelope(p);
-    if (c->knob_recs) q.loskip_wave_max = c->knob_loskip;
+    const crthip_params q = sync_blob(c, p, true);
     const dim3 gn((n + 63) / 64), b64(64);
     for (int passes = 1;; passes++) {
         HIPCHK(c, hipMemsetAsync(sc.changed, 0, sizeof(int), c->stream));
@@ -1674,9 +1614,8 @@ static int seq_row_tables(crthip_ctx *c, const crthip_params *p, int n_sets, int
     return CRTHIP_OK;
 }
 
-/* The phases.  Each *_body runs with the blob it is given: the caller's p, or -- c->knob_recs set: crthip_sequence_knobs, or a phase
- * entry point with bound records -- the library's copy of knobs_blob, whose KN kernels then read noise, monitor hue and saturation
- * (and bloom's max_e) per field.  Nothing of sequence mode's own arithmetic changes with that: rn advances once per sample whatever
+/* The phases.  Each *_body runs with the blob it is given: the caller's p, or -- crthip_sequence_knobs, or a phase entry point with
+ * bound records -- the blob of call_begin, whose KN kernels then read noise, monitor hue and saturation (and bloom's max_e) per field.  Nothing of sequence mode's own arithmetic changes with that: rn advances once per sample whatever
  * the gain (crt_core.c:358-366, so k_seq_rn's closed form holds), and the sync fixed point reads only the noisy signal. */
 /* phase 1: the noise generator of every field in closed form, all fields encoded in parallel (noise fused) */
 static int seq_encode_body(crthip_ctx *c, const crthip_params *p, int n, int first_index, int rn0,
@@ -1690,13 +1629,8 @@ static int seq_encode_body(crthip_ctx *c, const crthip_params *p, int n, int fir
     if (vhs && first_index != 0 && !c->vhs_prechained)
         return set_err(c, CRTHIP_E_ARG, "VHS: a video shares ONE rand() stream; its fields cannot start in the middle (first_index != 0)", hipSuccess);
     HIPCHK(c, hipSetDevice(c->device));
-    if (n > c->cap_fields) {
-        rc = crthip_reserve(c, n);
-        if (rc) return rc;
-    }
     c->seq_guess_n = 0;                                    /* a new video: no warm start for the sync chain */
-    c->last_n = 0;                                         /* (recorded below, once the signal is enqueued) */
-    rc = crt_run_encoder_prepare(c, p, true);
+    rc = encoder_ready(c, p, n, true);                     /* (the layout is recorded below, once the signal is enqueued) */
     if (rc) return rc;
     if (!vhs) {
         hipLaunchKernelGGL(k_seq_rn, dim3((n + 63) / 64), dim3(64), 0, c->stream, n, d_state, c->whole_field,
@@ -1827,41 +1761,21 @@ int crthip_seq_vhs_prechained(crthip_ctx *c, int on)
     return CRTHIP_OK;
 }
 
-/* The phase entry points.  Records bound with crthip_seq_bind_knobs: the phase runs on the library's copy of the blob (knobs_blob)
- * with c->knob_recs set for its duration; nothing bound: exactly the uniform phase.  c->knob_recs is cleared on every way out. */
-static int seq_phase_blob(crthip_ctx *c, const crthip_params *p, int n, crthip_params *q, const crthip_params **use)
-{
-    *use = p;
-    if (!c) return CRTHIP_OK;                             /* (refused by the body) */
-    c->knob_recs = nullptr;
-    if (!c->seq_knob_recs) return CRTHIP_OK;
-    int rc = check_params(c, p, n);
-    if (rc) return rc;
-    rc = knobs_blob(c, p, n, c->seq_knob_recs, &c->seq_knob_env, q);
-    if (rc) return rc;
-    c->knob_recs = c->seq_knob_recs;
-    *use = q;
-    return CRTHIP_OK;
-}
-
 int crthip_seq_bind_knobs(crthip_ctx *c, const crthip_knob_rec *d_recs, const crthip_knobs_env *env)
 {
     if (!c) return CRTHIP_E_ARG;
     if (!d_recs && !env) { c->seq_knob_recs = nullptr; return CRTHIP_OK; }
     if (!d_recs || !env) return set_err(c, CRTHIP_E_ARG, "crthip_seq_bind_knobs: records and env go together ((NULL, NULL) unbinds)", hipSuccess);
     if (CHECK_WORD(c, d_recs)) return CRTHIP_E_ARG;
-    if (env->magic != CRTHIP_KNOBS_MAGIC) return set_err(c, CRTHIP_E_ARG, "knobs: env does not come from crthip_knobs_prepare", hipSuccess);
-    if (c->sd.cc_samples == 5)
-        return set_err(c, CRTHIP_E_ARG, "knobs: the 5-sample decoder (PV-1000) takes monitor hue and saturation from the uniform parameters", hipSuccess);
-    if (env->n <= 0 || env->noise_max < 0 || env->sat_abs_max < 0) return set_err(c, CRTHIP_E_ARG, "knobs: env bounds", hipSuccess);
-    if (!knobs_env_pic_ok(env)) return set_err(c, CRTHIP_E_ARG, "knobs: the env's picture words contradict each other (not from crthip_knobs_prepare5)", hipSuccess);
+    const int rc = knobs_env_check(c, env, 0);
+    if (rc) return rc;
     c->seq_knob_recs = d_recs;
     c->seq_knob_env = *env;
     return CRTHIP_OK;
 }
 
 /* The encoder's level records for the knob entry points (crt_hip.h, LEVEL KNOBS): kept until unbound; checked against each call's n,
- * env and system by knobs_blob.  Nothing is copied or launched here. */
+ * env and system by call_begin.  Nothing is copied or launched here. */
 int crthip_bind_levels(crthip_ctx *c, const crthip_level_rec *d_levs, const crthip_levels_env *lenv)
 {
     if (!c) return CRTHIP_E_ARG;
@@ -1889,47 +1803,33 @@ int crthip_bind_hues(crthip_ctx *c, const crthip_hue_rec *d_hues, const crthip_h
     return CRTHIP_OK;
 }
 
+/* The phase entry points run with the records crthip_seq_bind_knobs has bound (call_begin, REC_SEQ_BOUND); nothing bound: exactly the
+ * uniform phase */
 int crthip_seq_encode(crthip_ctx *c, const crthip_params *p, int n, int first_index, int rn0,
                       const void *d_images, size_t istride, crthip_state *d_state)
 {
-    crthip_params q;
-    const crthip_params *use;
-    int rc = seq_phase_blob(c, p, n, &q, &use);
-    if (rc) return rc;
-    rc = seq_encode_body(c, use, n, first_index, rn0, d_images, istride, d_state);
-    if (c) c->knob_recs = nullptr;
-    return rc;
+    return with_records(c, p, n, REC_SEQ_BOUND, nullptr, nullptr, nullptr, nullptr, nullptr, [&](const crthip_params *q) {
+        return seq_encode_body(c, q, n, first_index, rn0, d_images, istride, d_state); });
 }
 
 int crthip_seq_sync(crthip_ctx *c, const crthip_params *p, int n, crthip_state *d_state, int hsync_in, int vsync_in,
                     int *hsync_out, int *vsync_out, int *passes_out)
 {
-    crthip_params q;
-    const crthip_params *use;
-    int rc = seq_phase_blob(c, p, n, &q, &use);
-    if (rc) return rc;
-    rc = seq_sync_body(c, use, n, d_state, hsync_in, vsync_in, hsync_out, vsync_out, passes_out);
-    if (c) c->knob_recs = nullptr;
-    return rc;
+    return with_records(c, p, n, REC_SEQ_BOUND, nullptr, nullptr, nullptr, nullptr, nullptr, [&](const crthip_params *q) {
+        return seq_sync_body(c, q, n, d_state, hsync_in, vsync_in, hsync_out, vsync_out, passes_out); });
 }
 
 int crthip_seq_decode(crthip_ctx *c, const crthip_params *p, int n, void *d_out, size_t ostride, crthip_state *d_state)
 {
-    crthip_params q;
-    const crthip_params *use;
-    int rc = seq_phase_blob(c, p, n, &q, &use);
-    if (rc) return rc;
-    rc = seq_decode_body(c, use, n, d_out, ostride, d_state);
-    if (c) c->knob_recs = nullptr;
-    return rc;
+    return with_records(c, p, n, REC_SEQ_BOUND, nullptr, nullptr, nullptr, nullptr, nullptr, [&](const crthip_params *q) {
+        return seq_decode_body(c, q, n, d_out, ostride, d_state); });
 }
 
-/* crthip_sequence, and crthip_sequence_knobs when c->knob_recs is set (p is then the library's copy carrying the call's bounds) */
+/* crthip_sequence and crthip_sequence_knobs, on the blob of the call's records (call_begin) */
 static int sequence_body(crthip_ctx *c, const crthip_params *p, int n, const void *d_images, size_t istride,
                          void *d_out, size_t ostride, const void *d_out_init, crthip_state *d_state, int *passes_out)
 {
-    int rc = check_params(c, p, n);
-    if (rc) return rc;
+    int rc;
     if (!d_images || !d_out || !d_state) return CRTHIP_E_ARG;
     if ((rc = check_images(c, p, d_images, istride)) || (rc = check_out(c, p, d_out, ostride, d_out_init, 0)) || (rc = CHECK_WORD(c, d_state))) return rc;
     if (p->out_bpp == 0) return CRTHIP_OK;                /* unknown output format: like crt_demodulate, nothing happens (crt_core.c:312-315) */
@@ -1949,73 +1849,27 @@ static int sequence_body(crthip_ctx *c, const crthip_params *p, int n, const voi
 int crthip_sequence(crthip_ctx *c, const crthip_params *p, int n, const void *d_images, size_t istride,
                     void *d_out, size_t ostride, const void *d_out_init, crthip_state *d_state, int *passes_out)
 {
-    if (c) c->knob_recs = nullptr;
-    return sequence_body(c, p, n, d_images, istride, d_out, ostride, d_out_init, d_state, passes_out);
+    return with_records(c, p, n, 0, nullptr, nullptr, nullptr, nullptr, nullptr, [&](const crthip_params *q) {
+        return sequence_body(c, q, n, d_images, istride, d_out, ostride, d_out_init, d_state, passes_out); });
 }
 
 int crthip_sequence_knobs(crthip_ctx *c, const crthip_params *p, int n, const void *d_images, size_t istride,
                           void *d_out, size_t ostride, const void *d_out_init, crthip_state *d_state,
                           const crthip_knob_rec *d_recs, const crthip_knobs_env *env, int *passes_out)
 {
-    int rc = check_params(c, p, n);
-    if (rc) return rc;
-    c->knob_recs = nullptr;
-    crthip_params q;
-    rc = knobs_blob(c, p, n, d_recs, env, &q);
-    if (rc) return rc;
-    c->knob_recs = d_recs;
-    rc = sequence_body(c, &q, n, d_images, istride, d_out, ostride, d_out_init, d_state, passes_out);
-    c->knob_recs = nullptr;
-    return rc;
+    return with_records(c, p, n, REC_KNOBS, d_recs, env, nullptr, nullptr, nullptr, [&](const crthip_params *q) {
+        return sequence_body(c, q, n, d_images, istride, d_out, ostride, d_out_init, d_state, passes_out); });
 }
 
-/* crthip_sequence_sets, and crthip_sequence_sets_knobs when d_recs is given: the call then runs on the library's copy of the blob
- * (knobs_blob over all n fields: record k belongs to field k of the batch, whatever its set) with c->knob_recs set by the caller */
-static int sequence_sets_body(crthip_ctx *c, const crthip_params *p, int n_sets, const int *set_first,
-                              const void *d_images, size_t istride, void *d_out, size_t ostride,
-                              const void *d_out_init, size_t out_init_stride, crthip_state *d_state, int *passes_out,
-                              const crthip_knob_rec *d_recs, const crthip_knobs_env *env)
+/* crthip_sequence_sets* behind its checks (sequence_sets_body), on the blob of the call's records: n fields in n_sets sets, the
+ * longest of max_len fields; streams = CRTHIP_F_VHS_SET_STREAMS */
+static int sequence_sets_run(crthip_ctx *c, const crthip_params *p, int n_sets, const int *set_first, int n, int max_len, bool streams,
+                             const void *d_images, size_t istride, void *d_out, size_t ostride,
+                             const void *d_out_init, size_t out_init_stride, crthip_state *d_state, int *passes_out)
 {
-    if (!c || !p) return CRTHIP_E_ARG;
-    if (n_sets <= 0 || !set_first) return set_err(c, CRTHIP_E_ARG, "crthip_sequence_sets: no sets", hipSuccess);
-    if (set_first[0] != 0) return set_err(c, CRTHIP_E_ARG, "crthip_sequence_sets: set_first[0] must be 0", hipSuccess);
-    int max_len = 0;
-    for (int s = 0; s < n_sets; s++) {
-        if (set_first[s + 1] <= set_first[s])
-            return set_err(c, CRTHIP_E_ARG, "crthip_sequence_sets: set_first must be strictly ascending (every set has at least one field)", hipSuccess);
-        if (set_first[s + 1] - set_first[s] > max_len) max_len = set_first[s + 1] - set_first[s];
-    }
-    const int n = set_first[n_sets];
-    int rc = check_params(c, p, n);
-    if (rc) return rc;
-    if (!d_images || !d_out || !d_state) return CRTHIP_E_ARG;
-    if ((rc = check_images(c, p, d_images, istride)) || (rc = check_out(c, p, d_out, ostride, d_out_init, out_init_stride)) || (rc = CHECK_WORD(c, d_state)) || (rc = CHECK_WORD(c, d_recs))) return rc;
-    if (p->out_bpp == 0) return CRTHIP_OK;                /* as crthip_sequence */
-    /* CRTHIP_F_VHS_SET_STREAMS: every set owns one rand() stream (hist[set_first[s]] = its generator before its first field) */
-    const bool streams = (p->flags & CRTHIP_F_VHS_SET_STREAMS) != 0;
-    if (streams && (c->system != CRTHIP_SYSTEM_NTSCVHS || (p->flags & CRTHIP_F_VHS_LCG_NOISE)))
-        return set_err(c, CRTHIP_E_ARG, "crthip_sequence_sets: CRTHIP_F_VHS_SET_STREAMS is for the VHS build with rand() noise "
-                                        "(CRTHIP_SYSTEM_NTSCVHS without CRTHIP_F_VHS_LCG_NOISE)", hipSuccess);
-    if (!streams && c->system == CRTHIP_SYSTEM_NTSCVHS && !(p->flags & CRTHIP_F_VHS_LCG_NOISE))
-        return set_err(c, CRTHIP_E_ARG, "crthip_sequence_sets: the VHS build with rand() noise is not available (every set would own a rand() stream); "
-                                        "use CRTHIP_F_VHS_LCG_NOISE or crthip_sequence per set", hipSuccess);
-    if (!streams && c->system == CRTHIP_SYSTEM_NTSCVHS && (p->flags & CRTHIP_F_VHS_DRAW_ABERRATION))
-        return set_err(c, CRTHIP_E_ARG, "crthip_sequence_sets: CRTHIP_F_VHS_DRAW_ABERRATION draws from the rand() stream; give the heights in d_state[k].aux", hipSuccess);
-    rc = seq_check(c, p, n);                              /* (streams: also that a history array is bound) */
-    if (rc) return rc;
-    crthip_params pk;
-    if (c->knob_recs) {
-        rc = knobs_blob(c, p, n, d_recs, env, &pk);
-        if (rc) return rc;
-        p = &pk;
-    }
     HIPCHK(c, hipSetDevice(c->device));
-    if (n > c->cap_fields) {
-        rc = crthip_reserve(c, n);
-        if (rc) return rc;
-    }
     SetsScratch sc;
-    rc = seq_carve(c, n_sets, n, p->outh, &sc);
+    int rc = seq_carve(c, n_sets, n, p->outh, &sc);
     if (rc) return rc;
     /* the set table: built here, uploaded once (the host copy belongs to the context: it outlives the copy) */
     const size_t tab_ints = (size_t) n_sets + 1, host_ints = ((tab_ints + 63) & ~(size_t) 63) + 2 * (size_t) n;
@@ -2033,9 +1887,8 @@ static int sequence_sets_body(crthip_ctx *c, const crthip_params *p, int n_sets,
         for (int k = set_first[s]; k < set_first[s + 1]; k++) { h_tab[2 * k] = set_first[s]; h_tab[2 * k + 1] = s; }
     HIPCHK(c, hipMemcpyAsync(sc.set_first, h_first, sizeof(int) * tab_ints, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(sc.tab, h_tab, sizeof(int2) * (size_t) n, hipMemcpyHostToDevice, c->stream));
-    /* as crthip_seq_encode: the encoder's tables, and the flat signal layout (recorded once the whole call is enqueued) */
-    c->last_n = 0;
-    rc = crt_run_encoder_prepare(c, p, true);
+    /* as crthip_seq_encode: the workspace, the encoder's tables, and the flat signal layout (recorded once the whole call is enqueued) */
+    rc = encoder_ready(c, p, n, true);
     if (rc) return rc;
     const dim3 gn((n + 63) / 64), gs((n_sets + 63) / 64), b64(64);
     hipLaunchKernelGGL(k_sets_incoming, gs, b64, 0, c->stream, n_sets, sc.set_first, d_state, sc.inc);
@@ -2072,13 +1925,51 @@ static int sequence_sets_body(crthip_ctx *c, const crthip_params *p, int n_sets,
     return CRTHIP_OK;
 }
 
+/* crthip_sequence_sets, and (kinds = REC_KNOBS) crthip_sequence_sets_knobs: what a sets call checks of its own, then the run with the
+ * call's records (call_begin over all n fields: record k belongs to field k of the batch, whatever its set) */
+static int sequence_sets_body(crthip_ctx *c, const crthip_params *p, int n_sets, const int *set_first,
+                              const void *d_images, size_t istride, void *d_out, size_t ostride,
+                              const void *d_out_init, size_t out_init_stride, crthip_state *d_state, int *passes_out,
+                              int kinds, const crthip_knob_rec *d_recs, const crthip_knobs_env *env)
+{
+    if (!c || !p) return CRTHIP_E_ARG;
+    if (n_sets <= 0 || !set_first) return set_err(c, CRTHIP_E_ARG, "crthip_sequence_sets: no sets", hipSuccess);
+    if (set_first[0] != 0) return set_err(c, CRTHIP_E_ARG, "crthip_sequence_sets: set_first[0] must be 0", hipSuccess);
+    int max_len = 0;
+    for (int s = 0; s < n_sets; s++) {
+        if (set_first[s + 1] <= set_first[s])
+            return set_err(c, CRTHIP_E_ARG, "crthip_sequence_sets: set_first must be strictly ascending (every set has at least one field)", hipSuccess);
+        if (set_first[s + 1] - set_first[s] > max_len) max_len = set_first[s + 1] - set_first[s];
+    }
+    const int n = set_first[n_sets];
+    int rc = check_params(c, p, n);
+    if (rc) return rc;
+    if (!d_images || !d_out || !d_state) return CRTHIP_E_ARG;
+    if ((rc = check_images(c, p, d_images, istride)) || (rc = check_out(c, p, d_out, ostride, d_out_init, out_init_stride)) || (rc = CHECK_WORD(c, d_state)) || (rc = CHECK_WORD(c, d_recs))) return rc;
+    if (p->out_bpp == 0) return CRTHIP_OK;                /* as crthip_sequence */
+    /* CRTHIP_F_VHS_SET_STREAMS: every set owns one rand() stream (hist[set_first[s]] = its generator before its first field) */
+    const bool streams = (p->flags & CRTHIP_F_VHS_SET_STREAMS) != 0;
+    if (streams && (c->system != CRTHIP_SYSTEM_NTSCVHS || (p->flags & CRTHIP_F_VHS_LCG_NOISE)))
+        return set_err(c, CRTHIP_E_ARG, "crthip_sequence_sets: CRTHIP_F_VHS_SET_STREAMS is for the VHS build with rand() noise "
+                                        "(CRTHIP_SYSTEM_NTSCVHS without CRTHIP_F_VHS_LCG_NOISE)", hipSuccess);
+    if (!streams && c->system == CRTHIP_SYSTEM_NTSCVHS && !(p->flags & CRTHIP_F_VHS_LCG_NOISE))
+        return set_err(c, CRTHIP_E_ARG, "crthip_sequence_sets: the VHS build with rand() noise is not available (every set would own a rand() stream); "
+                                        "use CRTHIP_F_VHS_LCG_NOISE or crthip_sequence per set", hipSuccess);
+    if (!streams && c->system == CRTHIP_SYSTEM_NTSCVHS && (p->flags & CRTHIP_F_VHS_DRAW_ABERRATION))
+        return set_err(c, CRTHIP_E_ARG, "crthip_sequence_sets: CRTHIP_F_VHS_DRAW_ABERRATION draws from the rand() stream; give the heights in d_state[k].aux", hipSuccess);
+    rc = seq_check(c, p, n);                              /* (streams: also that a history array is bound) */
+    if (rc) return rc;
+    return with_records(c, p, n, kinds, d_recs, env, nullptr, nullptr, nullptr, [&](const crthip_params *q) {
+        return sequence_sets_run(c, q, n_sets, set_first, n, max_len, streams, d_images, istride, d_out, ostride, d_out_init, out_init_stride,
+                                 d_state, passes_out); });
+}
+
 int crthip_sequence_sets(crthip_ctx *c, const crthip_params *p, int n_sets, const int *set_first,
                          const void *d_images, size_t istride, void *d_out, size_t ostride,
                          const void *d_out_init, size_t out_init_stride, crthip_state *d_state, int *passes_out)
 {
-    if (c) c->knob_recs = nullptr;
     return sequence_sets_body(c, p, n_sets, set_first, d_images, istride, d_out, ostride, d_out_init, out_init_stride, d_state, passes_out,
-                              nullptr, nullptr);
+                              0, nullptr, nullptr);
 }
 
 int crthip_sequence_sets_knobs(crthip_ctx *c, const crthip_params *p, int n_sets, const int *set_first,
@@ -2088,11 +1979,8 @@ int crthip_sequence_sets_knobs(crthip_ctx *c, const crthip_params *p, int n_sets
 {
     if (!c || !p) return CRTHIP_E_ARG;
     if (!d_recs || !env) return set_err(c, CRTHIP_E_ARG, "crthip_sequence_sets_knobs: no records / env", hipSuccess);
-    c->knob_recs = d_recs;
-    const int rc = sequence_sets_body(c, p, n_sets, set_first, d_images, istride, d_out, ostride, d_out_init, out_init_stride, d_state,
-                                      passes_out, d_recs, env);
-    c->knob_recs = nullptr;
-    return rc;
+    return sequence_sets_body(c, p, n_sets, set_first, d_images, istride, d_out, ostride, d_out_init, out_init_stride, d_state, passes_out,
+                              REC_KNOBS, d_recs, env);
 }
 
 int crthip_set_shape(crthip_ctx *c, int shape)

@@ -758,7 +758,7 @@ int crt_run_noise(crthip_ctx *c, const crthip_params *p, int n, const signed cha
                 const unsigned *tail_row = c->d_vhs_rows + (size_t) c->vhs_chunks * 31, *blk_rows = c->d_vhs_rows + (size_t) (c->vhs_chunks + 1) * 31;
                 const signed char *dig_blocks = c->d_vhs_dig + (size_t) c->vhs_chunks * VHS_DIG_ROW;
                 const bool mfma = c->vhs_mfma != 0;            /* the 31 x 31 jumps on the matrix cores (CRTHIP_VHS_MFMA=0: on the vector unit) */
-                const bool kn = c->knob_recs != nullptr;       /* per-field noise (crthip_fieldpass_knobs) */
+                const bool kn = c->call.knobs != nullptr;       /* per-field noise (crthip_fieldpass_knobs) */
 #define CRT_LAUNCH_TAIL(HOUT) do { \
                 if (kn && mfma) hipLaunchKernelGGL((k_vhs_tail<S, true, true>), dim3(n), dim3(64), 0, c->stream, *p, n, d_analog, d_inp, c->fstride, d_state, c->d_vhs_hist, HOUT, tail_row, blk_rows, dig_blocks); \
                 else if (kn) hipLaunchKernelGGL((k_vhs_tail<S, false, true>), dim3(n), dim3(64), 0, c->stream, *p, n, d_analog, d_inp, c->fstride, d_state, c->d_vhs_hist, HOUT, tail_row, blk_rows, dig_blocks); \
@@ -794,7 +794,7 @@ int crt_run_noise(crthip_ctx *c, const crthip_params *p, int n, const signed cha
         constexpr int CHUNKS = (S::INPUT_SIZE + 15) / 16;
         {
             ProfScope ps(c, CRTHIP_K_NOISE);
-            if (c->knob_recs)
+            if (c->call.knobs)
                 hipLaunchKernelGGL((k_noise<S, true>), dim3((n * CHUNKS + 255) / 256), dim3(256), 0, c->stream,
                                    *p, n, d_analog, d_inp, c->fstride, d_state, c->d_jump16);
             else

@@ -18,7 +18,7 @@
  * env, never the records: they are the caller's device memory and may be rewritten between two replays of a graph.  A record whose
  * image does not lie inside [images, images + extent), or that the instantiation cannot walk (the cooperative tiles move 16-byte
  * pieces of dword pixels: w >= 4, offset a multiple of 4), is replaced by the smallest image such a kernel reads, at offset 0 --
- * which the host has checked the extent for (sizes_blob, crt_host.hip).  The samples are then unspecified; the accesses are not.
+ * which the host has checked the extent for (call_begin, crt_host.hip).  The samples are then unspecified; the accesses are not.
  * col_step is NOT checked here: whatever it holds, every column it produces goes through size_col_clamped. */
 struct size_view { int w, h; unsigned long long off, cstep; };
 CRT_GUARD_FN size_view size_rec_checked(const crthip_size_rec &r, int in_bpp, bool spare_row, bool tiles, unsigned long long extent)

@@ -699,10 +699,10 @@ int crt_run_sync(crthip_ctx *c, const crthip_params *p, int n, const signed char
         const int shift = pad ? lay->shift : 0, padv = pad ? lay->padv : 0;
         const bool fpb4 = FPB4_OK && c->sync_kernel != 2 && (n >= SYNC_FPB4_MIN_FIELDS || c->sync_kernel == 3);
 #define CRTHIP_LAUNCH_SYNC(FPB, PADV) do { \
-    if (knob_pic_call(c)) \
+    if (c->call.pic) \
     hipLaunchKernelGGL((k_hsync_wave<S, FPB, PADV, 2>), dim3((n + FPB - 1) / FPB), dim3(64 * FPB), 0, c->stream, *p, n, d_inp, fstride, d_state, d_lines, \
                        c->whole_field, advance_rn, preset_ccf, shift, padv, pad ? const_cast<signed char *>(d_inp) : nullptr); \
-    else if (c->knob_recs) \
+    else if (c->call.knobs) \
     hipLaunchKernelGGL((k_hsync_wave<S, FPB, PADV, 1>), dim3((n + FPB - 1) / FPB), dim3(64 * FPB), 0, c->stream, *p, n, d_inp, fstride, d_state, d_lines, \
                        c->whole_field, advance_rn, preset_ccf, shift, padv, pad ? const_cast<signed char *>(d_inp) : nullptr); \
     else \
@@ -714,7 +714,7 @@ int crt_run_sync(crthip_ctx *c, const crthip_params *p, int n, const signed char
         }
         if (!fpb4) { if (pad) CRTHIP_LAUNCH_SYNC(1, true); else CRTHIP_LAUNCH_SYNC(1, false); }
 #undef CRTHIP_LAUNCH_SYNC
-        if (p->bloom && c->knob_recs)
+        if (p->bloom && c->call.knobs)
             hipLaunchKernelGGL((k_bloom<S, true>), dim3(n), dim3(256), 0, c->stream, *p, n, d_inp, fstride, d_lines);
         else if (p->bloom)
             hipLaunchKernelGGL((k_bloom<S>), dim3(n), dim3(256), 0, c->stream, *p, n, d_inp, fstride, d_lines);

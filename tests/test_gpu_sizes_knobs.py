@@ -398,6 +398,115 @@ def test_long_lived_context(crtlib):
     old.close()
 
 
+def test_every_way_in_and_out_of_a_record_call_leaves_nothing_behind(crtlib):
+    """ONE context through every record entry point -- field-passes, stills, sequences, sets and the bound phases, with levels and
+    hues bound from the first knob call until they are unbound -- and through a refused call of every family in between.  Every
+    accepted call equals the same call on a fresh context in out, state and (where the entry point leaves one) the signal; every
+    refused call leaves out and state as they were.  GPU against GPU: the oracle is pinned per entry point elsewhere, this pins only
+    that no call, accepted or refused, leaves anything of its records behind."""
+    import torch
+    case = "scale8"
+    n, w, h = len(ZK.CASES[case]["rows"]), 64, 48
+    images, rows = _device_layout(case), _rows(case)
+    assert rows.shape == (n, 8)                             # (n, 8): upload_knobs binds level and hue records
+    dev = torch.from_numpy(np.stack([R.synth_image(w, h + 1, 4, 500 + k) for k in range(n)])).to("cuda:0")
+    perm = [5, 4, 3, 2, 1, 0]
+    sched = [(0, 0, 0), (1, 0, 0), (1, 1, 0), (0, 0, 0)]
+    ragged = [0, 2, n]
+    vp = C.c_void_p
+
+    def uniform(s):
+        return crtlib.Settings(dev[:, :h], format=crtlib.FMT_BGRA, as_color=1, field=s.field, frame=s.frame, spare_row=True)
+
+    def phases(g, s):
+        g.seq_bind_knobs(rows[perm])
+        g.seq_encode(uniform(s), 0, 0, 194)
+        g.seq_sync(0, 0)
+        g.seq_decode()
+        g.seq_weave()
+
+    def unbind(g):
+        assert g.L.crthip_bind_levels(g.ctx, None, None) == 0 and g.L.crthip_bind_hues(g.ctx, None, None) == 0
+        g._levels_bound = g._hues_bound = False
+
+    def power_on(g):
+        g.out.zero_()
+        g.state.zero_()
+        g.state[:, crtlib.ST_RN] = 194
+
+    old, s_old = _make(crtlib, case)
+
+    def accepted(what, call, signal=True):
+        power_on(old)
+        call(old, s_old)
+        fresh, s_new = _make(crtlib, case)
+        call(fresh, s_new)
+        # the signal: CRT_INPUT_SIZE samples and the CRTHIP_TAIL mirror (16 bytes).  What crthip_fieldpass_signal copies behind them --
+        # the slack of its last 16-byte piece -- is the library's workspace, not signal (crt_hip.h, Buffer contract): a padded
+        # field-pass after a flat sequence call finds the sequence's samples there, in this library as in the one before it
+        sig_len = old.input_size + 16
+        for a, b, part in zip(_result(old, signal), _result(fresh, signal), ("out", "state", "inp")):
+            if part == "inp":
+                a, b = a[:, :sig_len], b[:, :sig_len]
+            np.testing.assert_array_equal(a, b, err_msg="%s %s" % (what, part))
+        fresh.close()
+
+    def refused(what, env, word, call, **bad):
+        """`call` with the fields `bad` of `env` altered for its duration: refused with `word`, out and state untouched"""
+        old._load_field_state(s_old)                        # (what the wrappers below write before they call)
+        old.synchronize()
+        out0, state0 = old.out.clone(), old.state.clone()
+        good = {a: getattr(env, a) for a in bad}
+        for a, v in bad.items():
+            setattr(env, a, v)
+        try:
+            with pytest.raises(RuntimeError, match=word):
+                call(old, s_old)
+        finally:
+            for a, v in good.items():
+                setattr(env, a, v)
+        old.synchronize()
+        assert torch.equal(old.out, out0) and torch.equal(old.state, state0), what + ": a refused call wrote"
+
+    accepted("fieldpass", lambda g, s: g.fieldpass(uniform(s), 24))
+    accepted("fieldpass_knobs", lambda g, s: g.fieldpass_knobs(uniform(s), rows))
+    kenv = old._knob_env
+    refused("fieldpass_knobs", kenv, "another number of fields", lambda g, s: g.fieldpass_knobs(uniform(s), None), n=n + 1)
+    accepted("stills_knobs", lambda g, s: g.stills_knobs(uniform(s), rows[perm], schedule=sched), signal=False)
+    kenv = old._knob_env
+    refused("stills_knobs", kenv, "another number of fields", lambda g, s: g.stills_knobs(uniform(s), None, schedule=sched), n=n + 1)
+    accepted("stills_sizes", lambda g, s: g.stills_sizes(images, 0, schedule=sched, settings=s), signal=False)
+    senv = old._size_env
+    refused("stills_sizes", senv, "another number of fields", lambda g, s: g.stills_sizes(None, 0, schedule=sched, settings=s), n=n + 1)
+    accepted("stills_sizes_knobs", lambda g, s: g.stills_sizes_knobs(images, rows, schedule=sched, settings=s), signal=False)
+    kenv = old._knob_env
+    # the sizes env is good, the knob env is not: nothing of the size records may stay behind either
+    refused("stills_sizes_knobs", kenv, "crthip_knobs_prepare", lambda g, s: g.stills_sizes_knobs(None, None, schedule=sched, settings=s),
+            magic=kenv.magic ^ 1)
+    refused("fieldpass_sizes_knobs", kenv, "another number of fields", lambda g, s: g.fieldpass_sizes_knobs(None, None, settings=s), n=n + 1)
+    accepted("sequence_knobs", lambda g, s: g.sequence_knobs(uniform(s), rows))
+    kenv = old._knob_env
+    refused("sequence_knobs", kenv, "another number of fields", lambda g, s: g.sequence_knobs(uniform(s), None), n=n + 1)
+    accepted("sequence_sets_knobs", lambda g, s: g.sequence_sets_knobs(uniform(s), rows[::-1].copy(), ragged))
+    kenv = old._knob_env
+    refused("sequence_sets_knobs", kenv, "another number of fields", lambda g, s: g.sequence_sets_knobs(uniform(s), None, ragged), n=n + 1)
+    accepted("the bound phases", phases)
+    kenv = old._knob_env
+    kenv.n = n + 1                                          # (the binding takes any n > 0: every phase checks it against its own)
+    assert old.L.crthip_seq_bind_knobs(old.ctx, vp(old.knob_recs.data_ptr()), C.byref(kenv)) == 0
+    kenv.n = n
+    refused("seq_encode", kenv, "another number of fields", lambda g, s: g.seq_encode(uniform(s), 0, 0, 194))
+    refused("seq_sync", kenv, "another number of fields", lambda g, s: g.seq_sync(0, 0))
+    refused("seq_decode", kenv, "another number of fields", lambda g, s: g.seq_decode())
+    unbind(old)                                             # (the phases' binding stays: no call below reads it)
+    accepted("fieldpass_knobs, nothing bound", lambda g, s: g.fieldpass_knobs(uniform(s), rows[:, :5].copy()))
+    accepted("fieldpass_sizes", lambda g, s: g.fieldpass_sizes(images, 24, settings=s))
+    accepted("stills", lambda g, s: g.stills(uniform(s), 24, schedule=sched), signal=False)
+    accepted("sequence", lambda g, s: g.sequence(uniform(s), 24))
+    accepted("fieldpass again", lambda g, s: g.fieldpass(uniform(s), 24))
+    old.close()
+
+
 @pytest.mark.parametrize("case", ["scale8", "hues"])
 def test_fenced_buffers(crtlib, case):
     """images packed with no slack inside a fenced allocation, d_out and d_state fenced too, VALID records: the payloads equal the

@@ -46,7 +46,7 @@ def test_prepare_field_by_field_against_finalize(lib, system):
         r = recs[k].view(np.int32)
         assert (r[0], r[1], r[2], r[3], r[4]) == (noise, q.huesn, q.huecs, sat, q.bloom_max_e), (system, k)
         assert not r[5:].any()
-        # the library's own envelope for a uniform batch with this field's noise (crt_host.hip, with_signal_envelope)
+        # the library's own envelope for a uniform batch with this field's noise (crt_host.hip, sync_blob)
         lo, hi = C.c_int(), C.c_int()
         L = lib.load_library()
         L.crt_setup_signal_range(C.byref(q), C.byref(lo), C.byref(hi))
