@@ -94,38 +94,26 @@ int crt_run_decode(crthip_ctx *c, const crthip_params *p, int n, const signed ch
         {
         const int total = n * S::LINES;
         const block_order bo = make_block_order((total + 63) / 64, c->dec_order_env == -1 ? n : c->dec_order_env);
-        const dim3 grid(bo.grid), block(64);
         unsigned char *o = (unsigned char *) d_out;
         ProfScope ps(c, CRTHIP_K_DECODE);
+        const auto group = [&](int tg, int rank) {                /* (the uniform call's part of decode_built, crt_decode_lane.h) */
+            return launch_decode<S, false, false>(c, p, n, d_inp, fstride, d_lines, o, ostride, tg, wide, fstage, fsa, min_tier, rank, nullptr, bo);
+        };
         for (int rank = 0; rank < passes; rank++) {
-#define CRTHIP_LAUNCH_DECODE(TG, B3) \
-    do { if constexpr (S::CCS != 4 && TG == 2) break; /* no FIR build of the 5-sample system */ \
-         if constexpr (S::CCS == 4 && TG == 0) { if (fstage) { /* float filter stages */ \
-             if (wide) hipLaunchKernelGGL((k_decode<S, TG, B3, 32, false, true>), grid, block, 0, c->stream, *p, n, d_inp, fstride, d_lines, o, ostride, min_tier, rank, (const int *) nullptr, bo.K, bo.per, fsa); \
-             else hipLaunchKernelGGL((k_decode<S, TG, B3, 16, false, true>), grid, block, 0, c->stream, *p, n, d_inp, fstride, d_lines, o, ostride, min_tier, rank, (const int *) nullptr, bo.K, bo.per, fsa); \
-             break; } } \
-         if (wide) hipLaunchKernelGGL((k_decode<S, TG, B3, 32>), grid, block, 0, c->stream, *p, n, d_inp, fstride, d_lines, o, ostride, min_tier, rank, (const int *) nullptr, bo.K, bo.per, fsa); \
-         else hipLaunchKernelGGL((k_decode<S, TG, B3, 16>), grid, block, 0, c->stream, *p, n, d_inp, fstride, d_lines, o, ostride, min_tier, rank, (const int *) nullptr, bo.K, bo.per, fsa); } while (0)
+            int rc = CRTHIP_OK;
             /* wide pictures in tiers 0 / 1: the 16-scanlines-per-wave kernel with 1 KB row runs (crt_decode4.hip); the groups
-             * of the higher tiers stay with k_decode below */
+             * of the higher tiers stay with k_decode */
             if (use_wide) {
-                const int rc = crt_run_decode_wide(c, p, n, d_inp, d_lines, d_out, ostride, min_tier, rank, fstride);
-                if (rc) return rc;
-                CRTHIP_LAUNCH_DECODE(1, false);
-                continue;
-            }
-            /* one launch per tier GROUP that can be populated (0: tiers 0 / 1, 1: tiers 2 / 3, 2: the FIR tiers); waves of the
-             * other group leave at once */
-            if (p->out_bpp == 3) {
-                if (min_tier <= 1) CRTHIP_LAUNCH_DECODE(0, true);
-                if (min_tier <= 3) CRTHIP_LAUNCH_DECODE(1, true);
-                if (min_tier >= 4) CRTHIP_LAUNCH_DECODE(2, true);
+                rc = crt_run_decode_wide(c, p, n, d_inp, d_lines, d_out, ostride, min_tier, rank, fstride);
+                if (rc == CRTHIP_OK) rc = group(1, rank);
             } else {
-                if (min_tier <= 1) CRTHIP_LAUNCH_DECODE(0, false);
-                if (min_tier <= 3) CRTHIP_LAUNCH_DECODE(1, false);
-                if (min_tier >= 4) CRTHIP_LAUNCH_DECODE(2, false);
+                /* one launch per tier GROUP that can be populated (0: tiers 0 / 1, 1: tiers 2 / 3, 2: the FIR tiers); waves of the
+                 * other group leave at once */
+                if (min_tier <= 1) rc = group(0, rank);
+                if (min_tier <= 3 && rc == CRTHIP_OK) rc = group(1, rank);
+                if (min_tier >= 4 && rc == CRTHIP_OK) rc = group(2, rank);
             }
-#undef CRTHIP_LAUNCH_DECODE
+            if (rc) return rc;
         }
         return CRTHIP_OK;
         }

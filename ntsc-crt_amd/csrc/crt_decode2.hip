@@ -304,20 +304,28 @@ int crt_run_decode_rows(crthip_ctx *c, const crthip_params *p, int n, const sign
         const int total = n * S::LINES;
         unsigned char *o = (unsigned char *) d_out;
         ProfScope ps(c, CRTHIP_K_DECODE);
+        /* tile of 16 samples: 9 KB of LDS per wave instead of 14 (4 waves per SIMD instead of 2.75) but twice the
+         * per-tile overheads: better once the launch has a few waves per SIMD (measured: batch 64
+         * -22 %, batch 16 and batch 1 +10 %, profiles/r02_shape_sweep.txt); CRTHIP_ROW_TILE=16|32 overrides */
+        const int ts = c->row_tile == 16 || (c->row_tile == 0 && n >= 48) ? 16 : 32;
+        /* k_decode_row<S, NARROW, BPP3, TS, PK>: every combination, PK (picture knobs: bright / contrast per scanline) for the 4-sample
+         * systems.  NARROW takes 4 scanlines per wave, the other instantiation 2; force_wide = it takes every group, not only the ones the
+         * narrow one leaves */
+        const auto rows = [&](bool narrow, int rank, int force_wide) {
+            return dispatch_int<16, 32>(ts, [&](auto ts_) {
+                return dispatch_bools([&](auto narrow_, auto b3, auto pk) {
+                    if constexpr (S::CCS == 4 || !pk) {
+                        hipLaunchKernelGGL((k_decode_row<S, narrow_, b3, ts_, pk>), dim3(narrow_ ? (total + 3) / 4 : (total + 1) / 2), dim3(64), 0, c->stream,
+                                           *p, n, d_inp, fstride, d_lines, o, ostride, rank, force_wide);
+                        return CRTHIP_OK;
+                    } else return launch_unbuilt(c, "k_decode_row");
+                }, narrow, p->out_bpp == 3, S::CCS == 4 && c->call.pic);
+            });
+        };
         for (int rank = 0; rank < passes; rank++) {
-#define CRTHIP_LAUNCH_ROWS_T(B3, TSV) \
-    do { if constexpr (S::CCS == 4) { if (c->call.pic) { /* picture knobs: bright / contrast per scanline */ \
-             if (narrow_ok) hipLaunchKernelGGL((k_decode_row<S, true, B3, TSV, true>), dim3((total + 3) / 4), dim3(64), 0, c->stream, *p, n, d_inp, fstride, d_lines, o, ostride, rank, 0); \
-             hipLaunchKernelGGL((k_decode_row<S, false, B3, TSV, true>), dim3((total + 1) / 2), dim3(64), 0, c->stream, *p, n, d_inp, fstride, d_lines, o, ostride, rank, narrow_ok ? 0 : 1); \
-             break; } } \
-         if (narrow_ok) hipLaunchKernelGGL((k_decode_row<S, true, B3, TSV>), dim3((total + 3) / 4), dim3(64), 0, c->stream, *p, n, d_inp, fstride, d_lines, o, ostride, rank, 0); \
-         hipLaunchKernelGGL((k_decode_row<S, false, B3, TSV>), dim3((total + 1) / 2), dim3(64), 0, c->stream, *p, n, d_inp, fstride, d_lines, o, ostride, rank, narrow_ok ? 0 : 1); } while (0)
-            /* tile of 16 samples: 9 KB of LDS per wave instead of 14 (4 waves per SIMD instead of 2.75) but twice the
-             * per-tile overheads: better once the launch has a few waves per SIMD (measured: batch 64
-             * -22 %, batch 16 and batch 1 +10 %, profiles/r02_shape_sweep.txt); CRTHIP_ROW_TILE=16|32 overrides */
-            if (c->row_tile == 16 || (c->row_tile == 0 && n >= 48)) { if (p->out_bpp == 3) CRTHIP_LAUNCH_ROWS_T(true, 16); else CRTHIP_LAUNCH_ROWS_T(false, 16); }
-            else { if (p->out_bpp == 3) CRTHIP_LAUNCH_ROWS_T(true, 32); else CRTHIP_LAUNCH_ROWS_T(false, 32); }
-#undef CRTHIP_LAUNCH_ROWS_T
+            int rc = narrow_ok ? rows(true, rank, 0) : CRTHIP_OK;
+            if (rc == CRTHIP_OK) rc = rows(false, rank, narrow_ok ? 0 : 1);
+            if (rc) return rc;
         }
         return CRTHIP_OK;
     });

@@ -149,29 +149,20 @@ int crt_run_decode_bloom_lanes(crthip_ctx *c, const crthip_params *p, int n, con
             const dim3 sgrid((total + 256 * BLOOM_SORT_ROUNDS - 1) / (256 * BLOOM_SORT_ROUNDS)), sblock(256);
             hipLaunchKernelGGL((k_bloom_count<S>), sgrid, sblock, 0, c->stream, total, p->outw, d_lines, hist);
             hipLaunchKernelGGL((k_bloom_scatter<S>), sgrid, sblock, 0, c->stream, total, p->outw, d_lines, hist, cursor, perm);
-            const dim3 grid((unsigned) (slots / 64)), block(64);
+            const block_order bo = { 0, 0, (unsigned) (slots / 64) };        /* the sort's order is the launch's */
             unsigned char *o = (unsigned char *) d_out;
+            /* the bloom part of decode_built (crt_decode_lane.h).  Picture knobs: bright / contrast per lane, the PK instantiations
+             * of the 4-sample systems; float filter stages (crt_decode.hip, crt_decode_fstages) otherwise */
+            const auto group = [&](int tg, int rank) {
+                return dispatch_bools([&](auto pk) {
+                    return launch_decode<S, true, pk>(c, p, n, d_inp, fstride, d_lines, o, ostride, tg, wide, fstage, fsa, min_tier, rank, perm, bo);
+                }, S::CCS == 4 && c->call.pic);
+            };
             for (int rank = 0; rank < passes; rank++) {
-#define CRTHIP_LAUNCH_BLOOM(TG, B3) \
-    do { if constexpr (S::CCS == 4) { if (c->call.pic) { /* picture knobs: bright / contrast per lane (crt_decode_lane.h, PK) */ \
-             if (wide) hipLaunchKernelGGL((k_decode<S, TG, B3, 32, true, false, true>), grid, block, 0, c->stream, *p, n, d_inp, fstride, d_lines, o, ostride, min_tier, rank, (const int *) perm, 0, 0, fsa); \
-             else hipLaunchKernelGGL((k_decode<S, TG, B3, 16, true, false, true>), grid, block, 0, c->stream, *p, n, d_inp, fstride, d_lines, o, ostride, min_tier, rank, (const int *) perm, 0, 0, fsa); \
-             break; } } \
-         if constexpr (S::CCS == 4 && TG == 0) { if (fstage) { /* float filter stages (crt_decode.hip, crt_decode_fstages) */ \
-             if (wide) hipLaunchKernelGGL((k_decode<S, TG, B3, 32, true, true>), grid, block, 0, c->stream, *p, n, d_inp, fstride, d_lines, o, ostride, min_tier, rank, (const int *) perm, 0, 0, fsa); \
-             else hipLaunchKernelGGL((k_decode<S, TG, B3, 16, true, true>), grid, block, 0, c->stream, *p, n, d_inp, fstride, d_lines, o, ostride, min_tier, rank, (const int *) perm, 0, 0, fsa); \
-             break; } } \
-         if (wide) hipLaunchKernelGGL((k_decode<S, TG, B3, 32, true>), grid, block, 0, c->stream, *p, n, d_inp, fstride, d_lines, o, ostride, min_tier, rank, (const int *) perm, 0, 0, fsa); \
-         else hipLaunchKernelGGL((k_decode<S, TG, B3, 16, true>), grid, block, 0, c->stream, *p, n, d_inp, fstride, d_lines, o, ostride, min_tier, rank, (const int *) perm, 0, 0, fsa); } while (0)
                 /* tier groups as in crt_run_decode: 0 = tiers 0 / 1 (tier 1 only ever holds lines of the 5-sample system here), 1 = 2 / 3 */
-                if (p->out_bpp == 3) {
-                    if (min_tier <= 1) CRTHIP_LAUNCH_BLOOM(0, true);
-                    CRTHIP_LAUNCH_BLOOM(1, true);
-                } else {
-                    if (min_tier <= 1) CRTHIP_LAUNCH_BLOOM(0, false);
-                    CRTHIP_LAUNCH_BLOOM(1, false);
-                }
-#undef CRTHIP_LAUNCH_BLOOM
+                int rc = min_tier <= 1 ? group(0, rank) : CRTHIP_OK;
+                if (rc == CRTHIP_OK) rc = group(1, rank);
+                if (rc) return rc;
             }
             return CRTHIP_OK;
         }

@@ -298,19 +298,14 @@ int crt_run_decode_wide(crthip_ctx *c, const crthip_params *p, int n, const sign
             const int nblk = (total + lpw - 1) / lpw;
             const block_order bo = make_block_order(nblk, c->wide_order_env == 0 || c->wide_order_env == -1 ? n : c->wide_order_env);
             const dim3 ogrid(bo.grid);
-            if (c->call.pic) {                         /* picture knobs: bright / contrast of the wave's field */
-                if (lpw == 8)
-                    hipLaunchKernelGGL((k_decode_wide<S, 8, true>), ogrid, block, 0, c->stream, *p, n, d_inp, fstride, d_lines, (unsigned char *) d_out, ostride,
+            /* k_decode_wide<S, LPW, PK>: both, with and without picture knobs (bright / contrast of the wave's field) */
+            return dispatch_int<8, 16>(lpw == 8 ? 8 : 16, [&](auto lpw_) {
+                return dispatch_bools([&](auto pk) {
+                    hipLaunchKernelGGL((k_decode_wide<S, lpw_, pk>), ogrid, block, 0, c->stream, *p, n, d_inp, fstride, d_lines, (unsigned char *) d_out, ostride,
                                        min_tier, rank, n_px, ppos_end, bo.K, bo.per);
-                else
-                    hipLaunchKernelGGL((k_decode_wide<S, 16, true>), ogrid, block, 0, c->stream, *p, n, d_inp, fstride, d_lines, (unsigned char *) d_out, ostride,
-                                       min_tier, rank, n_px, ppos_end, bo.K, bo.per);
-            } else if (lpw == 8)
-                hipLaunchKernelGGL((k_decode_wide<S, 8>), ogrid, block, 0, c->stream, *p, n, d_inp, fstride, d_lines, (unsigned char *) d_out, ostride,
-                                   min_tier, rank, n_px, ppos_end, bo.K, bo.per);
-            else
-                hipLaunchKernelGGL((k_decode_wide<S, 16>), ogrid, block, 0, c->stream, *p, n, d_inp, fstride, d_lines, (unsigned char *) d_out, ostride,
-                                   min_tier, rank, n_px, ppos_end, bo.K, bo.per);
+                    return CRTHIP_OK;
+                }, c->call.pic != 0);
+            });
         }
         return CRTHIP_OK;
     });

@@ -724,5 +724,35 @@ k_decode(const crthip_params P, int n_fields, const signed char *__restrict__ in
     else decode_lines(std::integral_constant<int, TLO + 1>{});
 }
 
+/* the k_decode instantiations that are built for system S (every pixel format and both pixel tiles of each): no FIR group for the
+ * bloom build (the 5-sample system's exists, and no call reaches it: crt_decode_check refuses its FIR build); float stages for tier
+ * group 0 of the 4-sample systems, without picture knobs; picture knobs for the 4-sample systems; no bloom build of the NES systems */
+template <class S> constexpr bool decode_built(int tg, bool bloom, bool fstage, bool pk)
+{
+    if (tg == 2 && bloom) return false;
+    if (fstage && !(S::CCS == 4 && tg == 0 && !pk)) return false;
+    if (pk && S::CCS != 4) return false;
+    return !(bloom && S::NES_TIMING);
+}
+/* One launch of tier group tg, for the three translation units that launch k_decode.  BLOOM and PK are the caller's: crt_decode.hip
+ * <false, false>, crt_decode_pk.hip <false, true>, crt_decode3.hip <true, either> -- each instantiates its own part of decode_built
+ * and nothing else.  fstage is the call's (crt_decode_fstages); the groups that have no float stages ignore it.  bo: the grid and
+ * the workgroup order; perm: the bloom sort's. */
+template <class S, bool BLOOM, bool PK>
+static int launch_decode(crthip_ctx *c, const crthip_params *p, int n, const signed char *d_inp, size_t fstride, const crthip_line *d_lines,
+                         unsigned char *o, size_t ostride, int tg, bool wide, bool fstage, const FStageArgs &fsa, int min_tier, int rank,
+                         const int *perm, const block_order &bo)
+{
+    return dispatch_int<0, 1, 2>(tg, [&](auto tg_) {
+        return dispatch_bools([&](auto b3, auto wide_, auto fs) {
+            if constexpr (decode_built<S>(tg_, BLOOM, fs, PK)) {
+                hipLaunchKernelGGL((k_decode<S, tg_, b3, wide_ ? 32 : 16, BLOOM, fs, PK>), dim3(bo.grid), dim3(64), 0, c->stream, *p, n, d_inp, fstride,
+                                   d_lines, o, ostride, min_tier, rank, perm, bo.K, bo.per, fsa);
+                return CRTHIP_OK;
+            } else return launch_unbuilt(c, "k_decode");
+        }, p->out_bpp == 3, wide, fstage && S::CCS == 4 && tg == 0 && !PK);
+    });
+}
+
 
 #endif

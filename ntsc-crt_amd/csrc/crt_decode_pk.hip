@@ -27,31 +27,24 @@ int crt_run_decode_pk(crthip_ctx *c, const crthip_params *p, int n, const signed
         } else {
             const int total = n * S::LINES;
             const block_order bo = make_block_order((total + 63) / 64, c->dec_order_env == -1 ? n : c->dec_order_env);
-            const dim3 grid(bo.grid), block(64);
             unsigned char *o = (unsigned char *) d_out;
             const FStageArgs fsa = {};
             ProfScope ps(c, CRTHIP_K_DECODE);
+            const auto group = [&](int tg, int rank) {            /* (the PK part of decode_built, crt_decode_lane.h) */
+                return launch_decode<S, false, true>(c, p, n, d_inp, fstride, d_lines, o, ostride, tg, wide, false, fsa, min_tier, rank, nullptr, bo);
+            };
             for (int rank = 0; rank < passes; rank++) {
-#define CRTHIP_LAUNCH_DECODE_PK(TG, B3) \
-    do { if (wide) hipLaunchKernelGGL((k_decode<S, TG, B3, 32, false, false, true>), grid, block, 0, c->stream, *p, n, d_inp, fstride, d_lines, o, ostride, min_tier, rank, (const int *) nullptr, bo.K, bo.per, fsa); \
-         else hipLaunchKernelGGL((k_decode<S, TG, B3, 16, false, false, true>), grid, block, 0, c->stream, *p, n, d_inp, fstride, d_lines, o, ostride, min_tier, rank, (const int *) nullptr, bo.K, bo.per, fsa); } while (0)
+                int rc = CRTHIP_OK;
                 if (use_wide) {
-                    const int rc = crt_run_decode_wide(c, p, n, d_inp, d_lines, d_out, ostride, min_tier, rank, fstride);
-                    if (rc) return rc;
-                    CRTHIP_LAUNCH_DECODE_PK(1, false);
-                    continue;
-                }
-                /* one launch per tier group that can be populated, as in crt_run_decode */
-                if (p->out_bpp == 3) {
-                    if (min_tier <= 1) CRTHIP_LAUNCH_DECODE_PK(0, true);
-                    if (min_tier <= 3) CRTHIP_LAUNCH_DECODE_PK(1, true);
-                    if (min_tier >= 4) CRTHIP_LAUNCH_DECODE_PK(2, true);
+                    rc = crt_run_decode_wide(c, p, n, d_inp, d_lines, d_out, ostride, min_tier, rank, fstride);
+                    if (rc == CRTHIP_OK) rc = group(1, rank);
                 } else {
-                    if (min_tier <= 1) CRTHIP_LAUNCH_DECODE_PK(0, false);
-                    if (min_tier <= 3) CRTHIP_LAUNCH_DECODE_PK(1, false);
-                    if (min_tier >= 4) CRTHIP_LAUNCH_DECODE_PK(2, false);
+                    /* one launch per tier group that can be populated, as in crt_run_decode */
+                    if (min_tier <= 1) rc = group(0, rank);
+                    if (min_tier <= 3 && rc == CRTHIP_OK) rc = group(1, rank);
+                    if (min_tier >= 4 && rc == CRTHIP_OK) rc = group(2, rank);
                 }
-#undef CRTHIP_LAUNCH_DECODE_PK
+                if (rc) return rc;
             }
             return CRTHIP_OK;
         }

@@ -34,6 +34,7 @@
 #include <string.h>
 
 #include <new>
+#include <type_traits>
 
 #include "crt_hip.h"
 #include "crt_setup.h"
@@ -461,7 +462,7 @@ __device__ __forceinline__ unsigned lcg_at(const uint2 *__restrict__ jump16, uns
  *
  * The col_step words are free in a call with size records: the SZ kernels take col_step from the record, and crthip_params_finalize's
  * check of them has passed on the caller's blob before the copy is made (a device pointer is never the 0 check_encoder looks for).
- * The one host-side reader of a blob's pointer is launch_active_sizes (crt_encode.hip): it sees a chunk's blob, not the chunk's first
+ * The one host-side reader of a blob's pointer is launch_active (crt_encode.hip; active_plain_blob): it sees a chunk's blob, not the chunk's first
  * field, so it takes the size records' pointer of a both call from there (size_blob_knobs_get) when it hands the plain SZ kernel a
  * copy with that pointer back in `reserved`. */
 static_assert(offsetof(crthip_params, ire_base) == offsetof(crthip_params, white) + sizeof(int), "white and ire_base are neighbours: one device pointer");
@@ -759,6 +760,31 @@ template <class F> static int dispatch_system(int system, int pattern, F &&fn)
     if (system == CRTHIP_SYSTEM_SNES) return fn(SysSNES{});
     if (system == CRTHIP_SYSTEM_TEMP) return fn(SysTEMP{});
     if (system == CRTHIP_SYSTEM_PV1K) return fn(SysPV1K{});
+    return CRTHIP_E_ARG;
+}
+
+/* The same idiom for a kernel's other template arguments -- every launch site turns its run-time flags into them HERE, and names its
+ * kernel in ONE hipLaunchKernelGGL inside the generic lambda it passes:
+ *   dispatch_bools(fn, a, b, ...)   returns fn(std::bool_constant<a>{}, std::bool_constant<b>{}, ...)
+ *   dispatch_int<16, 32>(v, fn)     returns fn(std::integral_constant<int, v>{}), an int, for v out of the list; CRTHIP_E_ARG otherwise
+ * The lambda sees every combination, so it launches under `if constexpr (<kernel>_built<S>(...))`, the constexpr predicate beside
+ * the kernel that says which instantiations exist: nothing outside it is compiled, and a combination outside it that a rule should
+ * ever ask for is an error (launch_unbuilt), never another kernel. */
+template <class F> static inline auto dispatch_bools(F &&fn) { return fn(); }
+template <class F, class... B> static inline auto dispatch_bools(F &&fn, bool b, B... rest)
+{
+    if (b) return dispatch_bools([&](auto... t) { return fn(std::true_type{}, t...); }, rest...);
+    return dispatch_bools([&](auto... t) { return fn(std::false_type{}, t...); }, rest...);
+}
+template <int... V, class F> static inline int dispatch_int(int v, F &&fn)
+{
+    int rc = CRTHIP_E_ARG;
+    (void) ((v == V ? (rc = fn(std::integral_constant<int, V>{}), true) : false) || ...);
+    return rc;
+}
+static inline int launch_unbuilt(crthip_ctx *c, const char *kernel)
+{
+    snprintf(c->err, sizeof(c->err), "internal error: no %s instantiation for this call's flags", kernel);
     return CRTHIP_E_ARG;
 }
 

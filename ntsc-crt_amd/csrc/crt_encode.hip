@@ -1346,98 +1346,21 @@ static bool encoder_fast_ok(const crthip_ctx *c, const crthip_params *p)
     return ok;
 }
 
-template <class S, bool FAST>
-static void launch_active_sizes(crthip_ctx *c, const crthip_params *p, int n, const void *d_images,
-                                signed char *dst, const crthip_state *d_state, const sig_layout &lay);
+/* ---- which instantiation a call launches: per kernel a constexpr predicate (what is built), a rule (what a call takes) and ONE
+ * launch that goes from the rule's answer to the template arguments through dispatch_bools / dispatch_int (crt_dev.h) ---- */
 
-template <class S, bool FULL, bool FAST>
-static void launch_active(crthip_ctx *c, const crthip_params *p, int n, const void *d_images, size_t istride,
-                          signed char *dst, const crthip_state *d_state, const sig_layout &lay)
+/* The (NOISE, CLAMP, KN, LV, HU) of every encoder kernel that has them, for system S.  The uniform call: with and without noise,
+ * into inp[] or not.  Records go with the fused path (CLAMP) only; KN is a noise gain, so there is none without NOISE; LV and HU exist
+ * for the 4-sample systems outside the PPU encoder, with the per-field noise or without any (a level or hue call is a knob call:
+ * NOISE == KN). */
+template <class S> constexpr bool enc_knobs_built(bool noise, bool clamp, bool kn, bool lv, bool hu)
 {
-    if constexpr (FULL && !S::IS_NES) {
-        if (c->call.sizes) { launch_active_sizes<S, FAST>(c, p, n, d_images, dst, d_state, lay); return; }
-    }
-    const int wrapn = lay.pitch != S::HRES ? lay.wrap : 0;      /* flat lines: a row that runs over its line's end simply continues */
-    ProfScope ps(c, CRTHIP_K_ACTIVE);
-    const int total = n * p->desth;
-    const dim3 grid((total + 63) / 64), block(64);
-    const unsigned char *img = (const unsigned char *) d_images;
-    if constexpr (S::IS_NES) {
-        if (p->w >= 8) {
-            /* the sample table depends on the black / white point only: rebuilt when those change, always on the
-             * context's main stream (crt_run_encoder_prepare), never concurrently with a reader */
-            if constexpr (FULL) {
-                if (p->noise != 0 && c->call.knobs) {
-                    hipLaunchKernelGGL((k_active_nes<S, true, true, 16, true>), grid, block, 0, c->stream, *p, n, img, istride, dst, lay.fstride, d_state, c->d_jump16, c->d_nes_tab, lay.pitch, lay.shift, wrapn);
-                    return;
-                }
-            }
-            if (FULL && p->noise != 0)
-                hipLaunchKernelGGL((k_active_nes<S, true, FULL, 16>), grid, block, 0, c->stream, *p, n, img, istride, dst, lay.fstride, d_state, c->d_jump16, c->d_nes_tab, lay.pitch, lay.shift, wrapn);
-            else
-                hipLaunchKernelGGL((k_active_nes<S, false, FULL, 16>), grid, block, 0, c->stream, *p, n, img, istride, dst, lay.fstride, d_state, c->d_jump16, c->d_nes_tab, lay.pitch, lay.shift, wrapn);
-            return;
-        }
-    }
-    const bool noise = FULL && p->noise != 0;
-    const bool kn = noise && c->call.knobs;                       /* per-field noise: the KN instantiations (fused path only) */
-    /* per-field black / white point: the LV instantiations -- every shape a knob call reaches below has one, with the per-field noise
-     * (kn: a level call is a knob call) or without any (the batch's largest noise is 0; the clean field of the rand()-noise VHS build
-     * and of CRT_DO_VSYNC 0).  The PPU encoder and the 5-sample system have none: such a call is refused (crt_host.hip, call_begin) */
-    constexpr bool LVS = FULL && !S::IS_NES && S::CCS == 4;
-    const bool lv = LVS && c->call.levels;
-    (void) lv;
-    /* per-field encoder hue: the HU instantiations, of the same shapes, with the level records (lv) or with the blob's white and
-     * ire_base (a hue-only binding) */
-    const bool hu = LVS && c->call.hues;
-    (void) hu;
-    if constexpr (!S::IS_NES) {
-        /* kernel shape (crthip_set_shape): small batches take the scanline-parallel encoder */
-        if (c->shape == 2 || (c->shape == 0 && n <= ROWS_SHAPE_MAX_FIELDS_ENC)) {
-            const dim3 rgrid((total + 7) / 8);
-            if constexpr (LVS) {
-#define CRTHIP_LAUNCH_ACTIVE_ROW_HU(NZ, KNV, LVV) \
-    hipLaunchKernelGGL((k_active_row<S, NZ, true, KNV, LVV, true>), rgrid, block, 0, c->stream, *p, n, img, istride, dst, lay.fstride, d_state, c->d_jump16, c->d_jump1, lay.pitch, lay.shift, wrapn)
-                if (hu) {
-                    if (lv) { if (kn) CRTHIP_LAUNCH_ACTIVE_ROW_HU(true, true, true); else CRTHIP_LAUNCH_ACTIVE_ROW_HU(false, false, true); }
-                    else    { if (kn) CRTHIP_LAUNCH_ACTIVE_ROW_HU(true, true, false); else CRTHIP_LAUNCH_ACTIVE_ROW_HU(false, false, false); }
-                    return;
-                }
-#undef CRTHIP_LAUNCH_ACTIVE_ROW_HU
-                if (lv) {
-                    if (kn) hipLaunchKernelGGL((k_active_row<S, true, true, true, true>), rgrid, block, 0, c->stream, *p, n, img, istride, dst, lay.fstride, d_state, c->d_jump16, c->d_jump1, lay.pitch, lay.shift, wrapn);
-                    else hipLaunchKernelGGL((k_active_row<S, false, true, false, true>), rgrid, block, 0, c->stream, *p, n, img, istride, dst, lay.fstride, d_state, c->d_jump16, c->d_jump1, lay.pitch, lay.shift, wrapn);
-                    return;
-                }
-            }
-            if constexpr (FULL) {
-                if (kn) {
-                    hipLaunchKernelGGL((k_active_row<S, true, true, true>), rgrid, block, 0, c->stream, *p, n, img, istride, dst, lay.fstride, d_state, c->d_jump16, c->d_jump1, lay.pitch, lay.shift, wrapn);
-                    return;
-                }
-            }
-            if (noise) hipLaunchKernelGGL((k_active_row<S, true, FULL>), rgrid, block, 0, c->stream, *p, n, img, istride, dst, lay.fstride, d_state, c->d_jump16, c->d_jump1, lay.pitch, lay.shift, wrapn);
-            else hipLaunchKernelGGL((k_active_row<S, false, FULL>), rgrid, block, 0, c->stream, *p, n, img, istride, dst, lay.fstride, d_state, c->d_jump16, c->d_jump1, lay.pitch, lay.shift, wrapn);
-            return;
-        }
-    }
-    const bool in4 = S::IS_NES || (p->in_bpp == 4 && p->w >= 4);
-    const block_order bo = make_block_order((int) grid.x, c->act_order_env == -1 ? n : c->act_order_env);
-    const dim3 ogrid(bo.grid);
-    const bool wide_in = c->ac_tile_env ? c->ac_tile_env == 32 : c->ac_tile ? c->ac_tile == 32 : p->w >= 1280;
-    /* Larger signal pieces where the batch keeps the chip full at the lower occupancy their tile leaves (fused throughput path,
-     * 4-byte pixels, fast envelope): 256-byte pieces beside the wide image tile (16.9 KB of LDS with the tile staged, 9 waves per CU), 128-byte pieces
-     * beside the narrow one (12.7 KB, 12 waves per CU).  Measured per batch size and system in profiles/r05_experiments.txt
-     * (sections 2-4): 1080p x 2048 k_active 0.86 -> 0.79 ms, 640x480 x 4096 1.05 -> 0.98, VHS / bloom / 720p -4..9 %; below the
-     * thresholds (crt_dev.h: by wave count, re-measured in round 6) and for the 5-sample system, whose carrier table shares the LDS, the
-     * 64-byte pieces stay the faster ones.
-     * CRTHIP_SIG_TILE=16 pins the small tile, =32 / =64 the large one whatever the batch (A/B). */
-    if constexpr (FULL && FAST && !S::IS_NES && S::CCS == 4) {
-        const unsigned nw = grid.x;
-        const bool big = c->sig_tile_env ? c->sig_tile_env != 16
-                       : wide_in ? nw >= (unsigned) SIG_TILE64_MIN_WAVES_WIDE
-                       : (nw > (unsigned) SIG_TILE32_BAND_LO && nw <= (unsigned) SIG_TILE32_ONE_ROUND) || nw > (unsigned) SIG_TILE16_ONE_ROUND;
-        if (in4 && big) {
+    if (!kn && !lv && !hu) return true;
+    if (!clamp || (kn && !noise)) return false;
+    if (lv || hu) return !S::IS_NES && S::CCS == 4 && noise == kn;
+    return true;
+}
+
 #ifndef CRTHIP_ENC_OL32
 /* dwords per row of the large sample tiles that are in LDS (RowTiles: staged when half of OT).  Measured (profiles/r06_ab_encoder_waves.txt):
  * the 64-dword tile beside the wide image tile gains from staging (9 instead of 6 waves per CU: 1280x720 x 2048 k_active 0.779 -> 0.744 ms,
@@ -1448,125 +1371,171 @@ static void launch_active(crthip_ctx *c, const crthip_params *p, int n, const vo
 #ifndef CRTHIP_ENC_OL64
 #define CRTHIP_ENC_OL64 32
 #endif
-#define CRTHIP_LAUNCH_ACTIVE_BIG(NZ, ...) \
-    do { if (wide_in) hipLaunchKernelGGL((k_active<S, NZ, true, true, true, 32, 64, CRTHIP_ENC_OL64 __VA_ARGS__>), ogrid, block, 0, c->stream, *p, n, img, istride, dst, lay.fstride, d_state, c->d_jump16, bo.K, bo.per, lay.pitch, lay.shift, wrapn); \
-         else hipLaunchKernelGGL((k_active<S, NZ, true, true, true, 16, 32, CRTHIP_ENC_OL32 __VA_ARGS__>), ogrid, block, 0, c->stream, *p, n, img, istride, dst, lay.fstride, d_state, c->d_jump16, bo.K, bo.per, lay.pitch, lay.shift, wrapn); } while (0)
-            if (hu) {
-                if (lv) { if (kn) CRTHIP_LAUNCH_ACTIVE_BIG(true, , true, true, true); else CRTHIP_LAUNCH_ACTIVE_BIG(false, , false, true, true); }
-                else    { if (kn) CRTHIP_LAUNCH_ACTIVE_BIG(true, , true, false, true); else CRTHIP_LAUNCH_ACTIVE_BIG(false, , false, false, true); }
-            }
-            else if (lv) { if (kn) CRTHIP_LAUNCH_ACTIVE_BIG(true, , true, true); else CRTHIP_LAUNCH_ACTIVE_BIG(false, , false, true); }
-            else if (kn) CRTHIP_LAUNCH_ACTIVE_BIG(true, , true);
-            else if (noise) CRTHIP_LAUNCH_ACTIVE_BIG(true); else CRTHIP_LAUNCH_ACTIVE_BIG(false);
-#undef CRTHIP_LAUNCH_ACTIVE_BIG
-            return;
-        }
-    }
-#define CRTHIP_LAUNCH_ACTIVE(NZ, I4, ...) \
-    do { if (wide_in) hipLaunchKernelGGL((k_active<S, NZ, FAST, I4, FULL, 32 __VA_ARGS__>), ogrid, block, 0, c->stream, *p, n, img, istride, dst, lay.fstride, d_state, c->d_jump16, bo.K, bo.per, lay.pitch, lay.shift, wrapn); \
-         else hipLaunchKernelGGL((k_active<S, NZ, FAST, I4, FULL, 16 __VA_ARGS__>), ogrid, block, 0, c->stream, *p, n, img, istride, dst, lay.fstride, d_state, c->d_jump16, bo.K, bo.per, lay.pitch, lay.shift, wrapn); } while (0)
-    if constexpr (LVS) {
-        if (hu) {                                                /* (the default tiles spelt out: KN, LV and HU are the last parameters) */
-#define CRTHIP_LAUNCH_ACTIVE_HU(NZ, KNV, LVV) \
-    do { if (in4) CRTHIP_LAUNCH_ACTIVE(NZ, true, , 16, 16, KNV, LVV, true); else CRTHIP_LAUNCH_ACTIVE(NZ, false, , 16, 16, KNV, LVV, true); } while (0)
-            if (lv) { if (kn) CRTHIP_LAUNCH_ACTIVE_HU(true, true, true); else CRTHIP_LAUNCH_ACTIVE_HU(false, false, true); }
-            else    { if (kn) CRTHIP_LAUNCH_ACTIVE_HU(true, true, false); else CRTHIP_LAUNCH_ACTIVE_HU(false, false, false); }
-#undef CRTHIP_LAUNCH_ACTIVE_HU
-            return;
-        }
-        if (lv) {                                                /* (the default tiles spelt out: KN and LV are the last parameters) */
-            if (kn) { if (in4) CRTHIP_LAUNCH_ACTIVE(true, true, , 16, 16, true, true); else CRTHIP_LAUNCH_ACTIVE(true, false, , 16, 16, true, true); }
-            else    { if (in4) CRTHIP_LAUNCH_ACTIVE(false, true, , 16, 16, false, true); else CRTHIP_LAUNCH_ACTIVE(false, false, , 16, 16, false, true); }
-            return;
-        }
-    }
-    if constexpr (FULL) {
-        if (kn) {                                                /* (the default tiles spelt out: KN is the last parameter) */
-            if (in4) CRTHIP_LAUNCH_ACTIVE(true, true, , 16, 16, true); else CRTHIP_LAUNCH_ACTIVE(true, false, , 16, 16, true);
-            return;
-        }
-    }
-    if (noise) { if (in4) CRTHIP_LAUNCH_ACTIVE(true, true); else CRTHIP_LAUNCH_ACTIVE(true, false); }
-    else       { if (in4) CRTHIP_LAUNCH_ACTIVE(false, true); else CRTHIP_LAUNCH_ACTIVE(false, false); }
-#undef CRTHIP_LAUNCH_ACTIVE
+
+/* One launch of the active rows: the kernel and its template arguments, by their names there (k_active has them all, k_active_row
+ * and k_active_nes a subset) */
+enum { ACTIVE_LANES, ACTIVE_ROWS, ACTIVE_NES };                   /* k_active, k_active_row, k_active_nes */
+struct ActiveVariant { int kernel; bool noise, fast, in4, clamp; int act, ot, ol; bool kn, lv, hu, sz; };
+
+/* the k_active instantiations that are built for system S */
+template <class S> constexpr bool active_built(const ActiveVariant &v)
+{
+    constexpr bool C4 = !S::IS_NES && S::CCS == 4;
+    const bool recs = v.kn || v.lv || v.hu;
+    if (!enc_knobs_built<S>(v.noise, v.clamp, v.kn, v.lv, v.hu)) return false;
+    /* SZ: the fused path of every system but the PPU encoder's; with records only where the knob entry points exist (4 samples) */
+    if (v.sz && (S::IS_NES || !v.clamp || (recs && !C4))) return false;
+    /* image tile: both widths; the SZ instantiations for bytewise pixels, which do not use it, with one */
+    if (v.act != 16 && v.act != 32) return false;
+    if (v.sz && !v.in4 && v.act != 16) return false;
+    /* signal tile: the 64-byte pieces everywhere; the large ones beside their image tile -- 4-byte pixels, fast envelope, fused path,
+     * 4-sample systems, and not for SZ with records (compile time: profiles/sizes_knobs_timing.txt) */
+    if (v.ot == 16 && v.ol == 16) return true;
+    if (!(C4 && v.fast && v.in4 && v.clamp) || (v.sz && recs)) return false;
+    return (v.act == 32 && v.ot == 64 && v.ol == CRTHIP_ENC_OL64) || (v.act == 16 && v.ot == 32 && v.ol == CRTHIP_ENC_OL32);
+}
+template <class S> constexpr bool active_row_built(bool noise, bool clamp, bool kn, bool lv, bool hu)
+{
+    return !S::IS_NES && enc_knobs_built<S>(noise, clamp, kn, lv, hu);
+}
+template <class S> constexpr bool active_nes_built(bool noise, bool clamp, bool kn)
+{
+    return S::IS_NES && enc_knobs_built<S>(noise, clamp, kn, false, false);
 }
 
-/* A sizes call (crthip_fieldpass_sizes / crthip_stills_sizes; c->call.sizes): k_active's SZ instantiations, always -- the lane-per-row
- * shape whatever crthip_set_shape says (crt_hip.h).  The grid gives every field ceil(desth / 64) whole wavefronts; what the uniform
- * launch decides by p->w is decided by the env's bounds, in ONE launch: the cooperative tiles need every row to hold a 16-byte piece
- * (w_min >= 4), the wide image tile pays where every image fills whole 128-byte lines (w_min >= 1280; CRTHIP_AC_TILE and
- * crthip_set_pixel_tile's encoder half override it as they do for the uniform launch).  The signal-tile rule is the uniform launch's, on
- * this launch's own wave count.  Every choice gives identical bytes (tests/test_gpu_sizes.py runs them against each other). */
-template <class S, bool FAST>
-static void launch_active_sizes(crthip_ctx *c, const crthip_params *p, int n, const void *d_images,
-                                signed char *dst, const crthip_state *d_state, const sig_layout &lay)
+/* wavefronts of a k_active launch: 64 rows of n * desth each, or -- a sizes call -- every field's ceil(desth / 64) whole ones */
+static int active_waves(const crthip_params *p, int n, bool sz)
 {
-    const int wrapn = lay.pitch != S::HRES ? lay.wrap : 0;
-    ProfScope ps(c, CRTHIP_K_ACTIVE);
-    const unsigned char *img = (const unsigned char *) d_images;
-    const size_t extent = ((size_t) c->call.size_env.extent_hi << 32) | c->call.size_env.extent_lo;
-    const int items = n * ((p->desth + 63) / 64);
-    const dim3 block(64);
-    const bool noise = p->noise != 0;
-    const bool in4 = p->in_bpp == 4 && c->call.size_env.w_min >= 4;
-    const block_order bo = make_block_order(items, c->act_order_env == -1 ? n : c->act_order_env);
-    const dim3 ogrid(bo.grid);
-    const bool wide_in = c->ac_tile_env ? c->ac_tile_env == 32 : c->ac_tile ? c->ac_tile == 32 : c->call.size_env.w_min >= 1280;
-    /* Sizes WITH knob records (crthip_fieldpass_sizes_knobs / crthip_stills_sizes_knobs; c->call.knobs as well): the SZ instantiations
-     * with KN (the batch's largest noise is not 0), LV (level records bound) and HU (hue records bound), in the three tile shapes below.
-     * The large signal tiles have no such instantiation (compile time: profiles/sizes_knobs_timing.txt) -- such a call takes the
-     * 64-byte pieces whatever its wave count, identical bytes.  A combined call that needs none of the three (noise 0 everywhere, nothing
-     * bound: the records then only reach the sync chain and the decoder) launches the plain SZ kernel, which looks for the size
-     * records in `reserved`: it gets a copy of the blob with the pointer there. */
-    crthip_params plain;
-    (void) plain;
-    if constexpr (S::CCS == 4) {
-        const bool lv = c->call.levels, hu = c->call.hues;
-        if (c->call.knobs && !noise && !lv && !hu) {
-            plain = *p;
-            blob_put_ptr(plain.reserved, size_blob_knobs_get(p));
-            p = &plain;                                            /* the plain launches below, with the copy */
-        } else if (c->call.knobs) {
-#define CRTHIP_LAUNCH_ACTIVE_SZK(I4, AC, KNV, LVV, HUV) \
-    hipLaunchKernelGGL((k_active<S, KNV, FAST, I4, true, AC, 16, 16, KNV, LVV, HUV, true>), ogrid, block, 0, c->stream, *p, n, img, extent, dst, lay.fstride, d_state, c->d_jump16, bo.K, bo.per, lay.pitch, lay.shift, wrapn)
-#define CRTHIP_LAUNCH_ACTIVE_SZK_TILE(KNV, LVV, HUV) \
-    do { if (!in4) CRTHIP_LAUNCH_ACTIVE_SZK(false, 16, KNV, LVV, HUV); else if (wide_in) CRTHIP_LAUNCH_ACTIVE_SZK(true, 32, KNV, LVV, HUV); else CRTHIP_LAUNCH_ACTIVE_SZK(true, 16, KNV, LVV, HUV); } while (0)
-            if (hu) {
-                if (lv) { if (noise) CRTHIP_LAUNCH_ACTIVE_SZK_TILE(true, true, true); else CRTHIP_LAUNCH_ACTIVE_SZK_TILE(false, true, true); }
-                else    { if (noise) CRTHIP_LAUNCH_ACTIVE_SZK_TILE(true, false, true); else CRTHIP_LAUNCH_ACTIVE_SZK_TILE(false, false, true); }
-            } else if (lv) {
-                if (noise) CRTHIP_LAUNCH_ACTIVE_SZK_TILE(true, true, false); else CRTHIP_LAUNCH_ACTIVE_SZK_TILE(false, true, false);
-            } else CRTHIP_LAUNCH_ACTIVE_SZK_TILE(true, false, false);
-#undef CRTHIP_LAUNCH_ACTIVE_SZK_TILE
-#undef CRTHIP_LAUNCH_ACTIVE_SZK
-            return;
-        }
-    }
-#define CRTHIP_LAUNCH_ACTIVE_SZ(NZ, FA, I4, AC, OTV, OLV) \
-    hipLaunchKernelGGL((k_active<S, NZ, FA, I4, true, AC, OTV, OLV, false, false, false, true>), ogrid, block, 0, c->stream, *p, n, img, extent, dst, lay.fstride, d_state, c->d_jump16, bo.K, bo.per, lay.pitch, lay.shift, wrapn)
-    if constexpr (FAST && S::CCS == 4) {
-        const unsigned nw = (unsigned) items;
+    return sz ? n * ((p->desth + 63) / 64) : (n * p->desth + 63) / 64;
+}
+
+/* The rule: what a call of n fields launches for its active rows.  full = the fused path (output is inp[]). */
+template <class S>
+static ActiveVariant active_variant(const crthip_ctx *c, const crthip_params *p, int n, bool full)
+{
+    constexpr bool C4 = !S::IS_NES && S::CCS == 4;
+    ActiveVariant v = {};
+    v.clamp = full;
+    v.fast = encoder_fast_ok<S>(c, p) && !c->force_exact;
+    /* A sizes call (crthip_fieldpass_sizes / crthip_stills_sizes; c->call.sizes): k_active's SZ instantiations, always -- the
+     * lane-per-row shape whatever crthip_set_shape says (crt_hip.h).  What the uniform launch decides by p->w is decided by the env's
+     * bounds, in ONE launch; every choice gives identical bytes (tests/test_gpu_sizes.py runs them against each other). */
+    v.sz = full && !S::IS_NES && c->call.sizes;
+    const int w = v.sz ? c->call.size_env.w_min : p->w;
+    v.noise = full && p->noise != 0;
+    /* per-field noise: the KN instantiations (fused path only).  Per-field black / white point: the LV instantiations -- every shape a
+     * knob call reaches has one, with the per-field noise (a level call is a knob call, call_begin) or without any (the batch's
+     * largest noise is 0; the clean field of the rand()-noise VHS build and of CRT_DO_VSYNC 0).  Per-field encoder hue: the HU
+     * instantiations, of the same shapes, with the level records or with the blob's white and ire_base (a hue-only binding).  The
+     * PPU encoder and the 5-sample system have neither: such a call is refused (crt_host.hip, call_begin). */
+    v.kn = v.noise && c->call.knobs;
+    v.lv = full && C4 && c->call.levels;
+    v.hu = full && C4 && c->call.hues;
+    v.act = v.ot = v.ol = 16;
+    /* the PPU encoder's sample table depends on the black / white point only: rebuilt when those change, always on the context's main
+     * stream (crt_run_encoder_prepare), never concurrently with a reader */
+    if (S::IS_NES && w >= 8) { v.kernel = ACTIVE_NES; return v; }
+    /* kernel shape (crthip_set_shape): small batches take the scanline-parallel encoder */
+    if (!S::IS_NES && !v.sz && (c->shape == 2 || (c->shape == 0 && n <= ROWS_SHAPE_MAX_FIELDS_ENC))) { v.kernel = ACTIVE_ROWS; return v; }
+    v.kernel = ACTIVE_LANES;
+    /* the cooperative tiles need every row to hold a 16-byte piece; the wide image tile pays where every image fills whole 128-byte
+     * lines (CRTHIP_AC_TILE and crthip_set_pixel_tile's encoder half override it) */
+    v.in4 = S::IS_NES || (p->in_bpp == 4 && w >= 4);
+    const bool wide_in = c->ac_tile_env ? c->ac_tile_env == 32 : c->ac_tile ? c->ac_tile == 32 : w >= 1280;
+    if (wide_in && (v.in4 || !v.sz)) v.act = 32;
+    /* Larger signal pieces where the batch keeps the chip full at the lower occupancy their tile leaves (fused throughput path,
+     * 4-byte pixels, fast envelope): 256-byte pieces beside the wide image tile (16.9 KB of LDS with the tile staged, 9 waves per CU), 128-byte pieces
+     * beside the narrow one (12.7 KB, 12 waves per CU).  Measured per batch size and system in profiles/r05_experiments.txt
+     * (sections 2-4): 1080p x 2048 k_active 0.86 -> 0.79 ms, 640x480 x 4096 1.05 -> 0.98, VHS / bloom / 720p -4..9 %; below the
+     * thresholds (crt_dev.h: by wave count, re-measured in round 6) and for the 5-sample system, whose carrier table shares the LDS, the
+     * 64-byte pieces stay the faster ones.  The rule is the same for a sizes call, on that launch's own wave count.
+     * CRTHIP_SIG_TILE=16 pins the small tile, =32 / =64 the large one whatever the batch (A/B).
+     * Sizes WITH knob records (crthip_fieldpass_sizes_knobs / crthip_stills_sizes_knobs) that need KN, LV or HU: the large tiles have
+     * no such instantiation -- the call takes the 64-byte pieces whatever its wave count, identical bytes. */
+    if (full && v.fast && C4 && v.in4 && !(v.sz && (v.kn || v.lv || v.hu))) {
+        const unsigned nw = (unsigned) active_waves(p, n, v.sz);
         const bool big = c->sig_tile_env ? c->sig_tile_env != 16
                        : wide_in ? nw >= (unsigned) SIG_TILE64_MIN_WAVES_WIDE
                        : (nw > (unsigned) SIG_TILE32_BAND_LO && nw <= (unsigned) SIG_TILE32_ONE_ROUND) || nw > (unsigned) SIG_TILE16_ONE_ROUND;
-        if (in4 && big) {
-            if (wide_in) { if (noise) CRTHIP_LAUNCH_ACTIVE_SZ(true, true, true, 32, 64, CRTHIP_ENC_OL64); else CRTHIP_LAUNCH_ACTIVE_SZ(false, true, true, 32, 64, CRTHIP_ENC_OL64); }
-            else         { if (noise) CRTHIP_LAUNCH_ACTIVE_SZ(true, true, true, 16, 32, CRTHIP_ENC_OL32); else CRTHIP_LAUNCH_ACTIVE_SZ(false, true, true, 16, 32, CRTHIP_ENC_OL32); }
-            return;
-        }
+        if (big) { v.ot = wide_in ? 64 : 32; v.ol = wide_in ? CRTHIP_ENC_OL64 : CRTHIP_ENC_OL32; }
     }
-    if (in4) {
-        if (wide_in) { if (noise) CRTHIP_LAUNCH_ACTIVE_SZ(true, FAST, true, 32, 16, 16); else CRTHIP_LAUNCH_ACTIVE_SZ(false, FAST, true, 32, 16, 16); }
-        else         { if (noise) CRTHIP_LAUNCH_ACTIVE_SZ(true, FAST, true, 16, 16, 16); else CRTHIP_LAUNCH_ACTIVE_SZ(false, FAST, true, 16, 16, 16); }
-    } else {                                                     /* (bytewise pixels: the image tile is not used, one width of it serves) */
-        if (noise) CRTHIP_LAUNCH_ACTIVE_SZ(true, FAST, false, 16, 16, 16); else CRTHIP_LAUNCH_ACTIVE_SZ(false, FAST, false, 16, 16, 16);
-    }
-#undef CRTHIP_LAUNCH_ACTIVE_SZ
+    return v;
 }
+/* ... and a sizes call with knob records that needs none of KN, LV and HU (noise 0 everywhere, nothing bound: the records then only
+ * reach the sync chain and the decoder) launches the plain SZ kernel, which looks for the size records in `reserved`: it gets a copy
+ * of the blob with the pointer there */
+static bool active_plain_blob(const crthip_ctx *c, const ActiveVariant &v)
+{
+    return v.sz && c->call.knobs && !v.kn && !v.lv && !v.hu;
+}
+
+/* v -> the kernel.  Every run-time value below comes out of active_variant; a variant outside the predicates is an error. */
+template <class S>
+static int launch_active(crthip_ctx *c, const crthip_params *p, int n, const void *d_images, size_t istride,
+                         signed char *dst, const crthip_state *d_state, const sig_layout &lay, bool full)
+{
+    const ActiveVariant v = active_variant<S>(c, p, n, full);
+    const int wrapn = lay.pitch != S::HRES ? lay.wrap : 0;      /* flat lines: a row that runs over its line's end simply continues */
+    ProfScope ps(c, CRTHIP_K_ACTIVE);
+    const unsigned char *img = (const unsigned char *) d_images;
+    const int waves = active_waves(p, n, v.sz);
+    const dim3 block(64);
+    if (v.kernel == ACTIVE_NES)
+        return dispatch_bools([&](auto noise, auto clamp, auto kn) {
+            if constexpr (active_nes_built<S>(noise, clamp, kn)) {
+                hipLaunchKernelGGL((k_active_nes<S, noise, clamp, 16, kn>), dim3(waves), block, 0, c->stream, *p, n, img, istride, dst, lay.fstride,
+                                   d_state, c->d_jump16, c->d_nes_tab, lay.pitch, lay.shift, wrapn);
+                return CRTHIP_OK;
+            } else return launch_unbuilt(c, "k_active_nes");
+        }, v.noise, v.clamp, v.kn);
+    if (v.kernel == ACTIVE_ROWS)
+        return dispatch_bools([&](auto noise, auto clamp, auto kn, auto lv, auto hu) {
+            if constexpr (active_row_built<S>(noise, clamp, kn, lv, hu)) {
+                hipLaunchKernelGGL((k_active_row<S, noise, clamp, kn, lv, hu>), dim3((n * p->desth + 7) / 8), block, 0, c->stream, *p, n, img, istride,
+                                   dst, lay.fstride, d_state, c->d_jump16, c->d_jump1, lay.pitch, lay.shift, wrapn);
+                return CRTHIP_OK;
+            } else return launch_unbuilt(c, "k_active_row");
+        }, v.noise, v.clamp, v.kn, v.lv, v.hu);
+    crthip_params plain;
+    if (active_plain_blob(c, v)) {
+        plain = *p;
+        blob_put_ptr(plain.reserved, size_blob_knobs_get(p));
+        p = &plain;
+    }
+    /* (SZ: `istride` carries the extent of the image buffer) */
+    if (v.sz) istride = ((size_t) c->call.size_env.extent_hi << 32) | c->call.size_env.extent_lo;
+    const block_order bo = make_block_order(waves, c->act_order_env == -1 ? n : c->act_order_env);
+    return dispatch_int<16, 32>(v.act, [&](auto act) { return dispatch_int<16, 32, 64>(v.ot, [&](auto ot) {
+        return dispatch_bools([&](auto noise, auto fast, auto in4, auto clamp, auto kn, auto lv, auto hu, auto sz) {
+            constexpr int OL = ot == 64 ? CRTHIP_ENC_OL64 : ot == 32 ? CRTHIP_ENC_OL32 : 16;
+            constexpr ActiveVariant V = { ACTIVE_LANES, noise, fast, in4, clamp, act, ot, OL, kn, lv, hu, sz };
+            if constexpr (active_built<S>(V)) {
+                if (v.ol != OL) return launch_unbuilt(c, "k_active");
+                hipLaunchKernelGGL((k_active<S, noise, fast, in4, clamp, act, ot, OL, kn, lv, hu, sz>), dim3(bo.grid), block, 0, c->stream, *p, n, img,
+                                   istride, dst, lay.fstride, d_state, c->d_jump16, bo.K, bo.per, lay.pitch, lay.shift, wrapn);
+                return CRTHIP_OK;
+            } else return launch_unbuilt(c, "k_active");
+        }, v.noise, v.fast, v.in4, v.clamp, v.kn, v.lv, v.hu, v.sz);
+    }); });
+}
+
+/* the margin kernels' (NOISE, KN, HU): what is built, and what a call takes (a hue call is a knob call: its noise is per field, or
+ * the batch's largest is 0) */
+struct MarginVariant { bool noise, kn, hu; };
+template <class S> constexpr bool margin_built(bool noise, bool kn, bool hu) { return enc_knobs_built<S>(noise, true, kn, false, hu); }
+template <class S> static MarginVariant margin_variant(const crthip_ctx *c, const crthip_params *p)
+{
+    MarginVariant v;
+    v.noise = p->noise != 0;
+    v.kn = v.noise && c->call.knobs;
+    v.hu = !S::IS_NES && S::CCS == 4 && c->call.hues;
+    return v;
+}
+
 
 /* fused path: skeleton + noise for everything outside the active rectangle */
 template <class S>
-static void launch_margins(crthip_ctx *c, const crthip_params *p, int n, signed char *dst, const crthip_state *d_state)
+static int launch_margins(crthip_ctx *c, const crthip_params *p, int n, signed char *dst, const crthip_state *d_state)
 {
     ProfScope ps(c, CRTHIP_K_TEMPLATE);
     const int s0 = p->yo * S::HRES + p->xo;
@@ -1577,32 +1546,19 @@ static void launch_margins(crthip_ctx *c, const crthip_params *p, int n, signed 
     const int per_field = head + (p->desth - 1) * gap + tail;
     const unsigned gap_magic = gap > 0 ? (unsigned) ((0x100000000ull + (unsigned) gap - 1) / (unsigned) gap) : 0u;
     const dim3 grid((per_field + 255) / 256, n < 65535 ? n : 65535);          /* (fields beyond the grid's y limit: the kernel loops) */
-    if constexpr (!S::IS_NES && S::CCS == 4) {
-        if (c->call.hues) {                                       /* (a knob call: its noise is per field, or the batch's largest is 0) */
-            if (p->noise != 0)
-                hipLaunchKernelGGL((k_margin<S, true, true, true>), grid, dim3(256), 0, c->stream,
-                                   *p, n, dst, c->fstride, d_state, c->d_jump16, c->d_jump1, c->d_skel, head, gap, tail, gap_magic);
-            else
-                hipLaunchKernelGGL((k_margin<S, false, false, true>), grid, dim3(256), 0, c->stream,
-                                   *p, n, dst, c->fstride, d_state, c->d_jump16, c->d_jump1, c->d_skel, head, gap, tail, gap_magic);
-            return;
-        }
-    }
-    if (p->noise != 0 && c->call.knobs)
-        hipLaunchKernelGGL((k_margin<S, true, true>), grid, dim3(256), 0, c->stream,
-                           *p, n, dst, c->fstride, d_state, c->d_jump16, c->d_jump1, c->d_skel, head, gap, tail, gap_magic);
-    else if (p->noise != 0)
-        hipLaunchKernelGGL((k_margin<S, true>), grid, dim3(256), 0, c->stream,
-                           *p, n, dst, c->fstride, d_state, c->d_jump16, c->d_jump1, c->d_skel, head, gap, tail, gap_magic);
-    else
-        hipLaunchKernelGGL((k_margin<S, false>), grid, dim3(256), 0, c->stream,
-                           *p, n, dst, c->fstride, d_state, c->d_jump16, c->d_jump1, c->d_skel, head, gap, tail, gap_magic);
+    const MarginVariant v = margin_variant<S>(c, p);
+    return dispatch_bools([&](auto noise, auto kn, auto hu) {
+        if constexpr (margin_built<S>(noise, kn, hu)) {
+            hipLaunchKernelGGL((k_margin<S, noise, kn, hu>), grid, dim3(256), 0, c->stream,
+                               *p, n, dst, c->fstride, d_state, c->d_jump16, c->d_jump1, c->d_skel, head, gap, tail, gap_magic);
+            return CRTHIP_OK;
+        } else return launch_unbuilt(c, "k_margin");
+    }, v.noise, v.kn, v.hu);
 }
-
 
 /* ... into padded signal lines (k_margin_pad) */
 template <class S>
-static void launch_margins_padded(crthip_ctx *c, const crthip_params *p, int n, signed char *dst, const crthip_state *d_state, const sig_layout &lay)
+static int launch_margins_padded(crthip_ctx *c, const crthip_params *p, int n, signed char *dst, const crthip_state *d_state, const sig_layout &lay)
 {
     ProfScope ps(c, CRTHIP_K_TEMPLATE);
     constexpr int CF = (S::HRES + 15) / 16;
@@ -1613,34 +1569,14 @@ static void launch_margins_padded(crthip_ctx *c, const crthip_params *p, int n, 
     const unsigned act_magic = act_per > 1 ? (unsigned) ((0x100000000ull + (unsigned) act_per - 1) / (unsigned) act_per) : 0u;
     const int per_field = p->yo * CF + p->desth * act_per + (S::VRES - p->yo - p->desth) * CF;
     const dim3 grid((per_field + 255) / 256, n < 65535 ? n : 65535);
-    if constexpr (!S::IS_NES && S::CCS == 4) {
-        if (c->call.hues) {
-            if (p->noise != 0)
-                hipLaunchKernelGGL((k_margin_pad<S, true, true, true>), grid, dim3(256), 0, c->stream, *p, n, dst, lay.fstride, lay.shift, d_state,
-                                   c->d_jump16, c->d_jump1, c->d_skel, c->fstride, cl, cr, act_magic, lay.wrap);
-            else
-                hipLaunchKernelGGL((k_margin_pad<S, false, false, true>), grid, dim3(256), 0, c->stream, *p, n, dst, lay.fstride, lay.shift, d_state,
-                                   c->d_jump16, c->d_jump1, c->d_skel, c->fstride, cl, cr, act_magic, lay.wrap);
-            return;
-        }
-    }
-    if (p->noise != 0 && c->call.knobs)
-        hipLaunchKernelGGL((k_margin_pad<S, true, true>), grid, dim3(256), 0, c->stream, *p, n, dst, lay.fstride, lay.shift, d_state,
-                           c->d_jump16, c->d_jump1, c->d_skel, c->fstride, cl, cr, act_magic, lay.wrap);
-    else if (p->noise != 0)
-        hipLaunchKernelGGL((k_margin_pad<S, true>), grid, dim3(256), 0, c->stream, *p, n, dst, lay.fstride, lay.shift, d_state,
-                           c->d_jump16, c->d_jump1, c->d_skel, c->fstride, cl, cr, act_magic, lay.wrap);
-    else
-        hipLaunchKernelGGL((k_margin_pad<S, false>), grid, dim3(256), 0, c->stream, *p, n, dst, lay.fstride, lay.shift, d_state,
-                           c->d_jump16, c->d_jump1, c->d_skel, c->fstride, cl, cr, act_magic, lay.wrap);
-}
-
-template <class S, bool FULL>
-static void launch_active_any(crthip_ctx *c, const crthip_params *p, int n, const void *d_images, size_t istride,
-                              signed char *dst, const crthip_state *d_state, const sig_layout &lay)
-{
-    if (encoder_fast_ok<S>(c, p) && !c->force_exact) launch_active<S, FULL, true>(c, p, n, d_images, istride, dst, d_state, lay);
-    else launch_active<S, FULL, false>(c, p, n, d_images, istride, dst, d_state, lay);
+    const MarginVariant v = margin_variant<S>(c, p);
+    return dispatch_bools([&](auto noise, auto kn, auto hu) {
+        if constexpr (margin_built<S>(noise, kn, hu)) {
+            hipLaunchKernelGGL((k_margin_pad<S, noise, kn, hu>), grid, dim3(256), 0, c->stream, *p, n, dst, lay.fstride, lay.shift, d_state,
+                               c->d_jump16, c->d_jump1, c->d_skel, c->fstride, cl, cr, act_magic, lay.wrap);
+            return CRTHIP_OK;
+        } else return launch_unbuilt(c, "k_margin_pad");
+    }, v.noise, v.kn, v.hu);
 }
 
 template <class S, bool FULL>
@@ -1654,6 +1590,7 @@ static int launch_encoder(crthip_ctx *c, const crthip_params *p, int n, const vo
      * is being taken (per-kernel durations are of kernels running alone), not on the internal stream itself (overlap chunks).
      * CRTHIP_MARGIN_SIDE=0: in sequence (A/B: profiles/r06_ab_margin_side.txt). */
     bool side = false;
+    int rc = CRTHIP_OK;
     if (FULL) {
         side = c->margin_side && c->aux_stream && c->ev_mfork && !c->prof && n >= MARGIN_SIDE_MIN_FIELDS && c->stream != c->aux_stream;
         hipStream_t main_stream = c->stream;
@@ -1661,8 +1598,8 @@ static int launch_encoder(crthip_ctx *c, const crthip_params *p, int n, const vo
             if (hipEventRecord(c->ev_mfork, main_stream) != hipSuccess || hipStreamWaitEvent(c->aux_stream, c->ev_mfork, 0) != hipSuccess) side = false;
             else c->stream = c->aux_stream;
         }
-        if (lay.pitch != S::HRES) launch_margins_padded<S>(c, p, n, dst, d_state, lay);
-        else launch_margins<S>(c, p, n, dst, d_state);
+        if (lay.pitch != S::HRES) rc = launch_margins_padded<S>(c, p, n, dst, d_state, lay);
+        else rc = launch_margins<S>(c, p, n, dst, d_state);
         if (side) {
             c->stream = main_stream;
             if (hipEventRecord(c->ev_mjoin, c->aux_stream) != hipSuccess) return CRTHIP_E_HIP;
@@ -1674,9 +1611,9 @@ static int launch_encoder(crthip_ctx *c, const crthip_params *p, int n, const vo
         hipLaunchKernelGGL((k_template<S>), dim3((total + 255) / 256), dim3(256), 0, c->stream,
                            *p, n, dst, c->fstride, d_state, nes_setup);
     }
-    launch_active_any<S, FULL>(c, p, n, d_images, istride, dst, d_state, lay);
+    if (rc == CRTHIP_OK) rc = launch_active<S>(c, p, n, d_images, istride, dst, d_state, lay, FULL);
     if (side && hipStreamWaitEvent(c->stream, c->ev_mjoin, 0) != hipSuccess) return CRTHIP_E_HIP;
-    return CRTHIP_OK;
+    return rc;
 }
 
 /* after crt_modulate: ccf preset (crt_ntsc.c:325-329, crt_nes.c:196-200, crt_snes.c:238-240,321-325),
@@ -1720,13 +1657,10 @@ __global__ void k_encoder_state(const crthip_params P, int n_fields, crthip_stat
 template <class S>
 static void launch_encoder_state(crthip_ctx *c, const crthip_params *p, int n, crthip_state *d_state)
 {
-    if constexpr (!S::IS_NES && S::CCS == 4) {
-        if (c->call.hues) {
-            hipLaunchKernelGGL((k_encoder_state<S, true>), dim3((n + 63) / 64), dim3(64), 0, c->stream, *p, n, d_state);
-            return;
-        }
-    }
-    hipLaunchKernelGGL((k_encoder_state<S>), dim3((n + 63) / 64), dim3(64), 0, c->stream, *p, n, d_state);
+    constexpr bool C4 = !S::IS_NES && S::CCS == 4;                /* HU: built for these systems, taken by a call with hue records */
+    dispatch_bools([&](auto hu) {
+        if constexpr (C4 || !hu) hipLaunchKernelGGL((k_encoder_state<S, hu>), dim3((n + 63) / 64), dim3(64), 0, c->stream, *p, n, d_state);
+    }, C4 && c->call.hues);
 }
 
 /* Encoder tables that depend on the parameter blob only (clean skeleton variants, NES sample table): (re)built on
@@ -1808,12 +1742,9 @@ int crt_run_encoder_prepare(crthip_ctx *c, const crthip_params *p, bool fused)
             signed char *dst = table_target(c, &c->d_skel, &c->d_skel_alt, (size_t) SKEL_VARIANTS * c->fstride, capturing || c->skel_captured);
             if (!dst) rc = set_err(c, CRTHIP_E_NOMEM, "hipMalloc skeleton tables", hipSuccess);
             else {
-                if (!capturing) {
-                    ProfScope ps(c, CRTHIP_K_TEMPLATE);
-                    hipLaunchKernelGGL((k_skeleton<S>), dim3((SK_LANES + 255) / 256), dim3(256), 0, st, *p, dst, c->fstride);
-                } else {
-                    hipLaunchKernelGGL((k_skeleton<S>), dim3((SK_LANES + 255) / 256), dim3(256), 0, st, *p, dst, c->fstride);
-                }
+                const auto build = [&] { hipLaunchKernelGGL((k_skeleton<S>), dim3((SK_LANES + 255) / 256), dim3(256), 0, st, *p, dst, c->fstride); };
+                if (capturing) build();                        /* (on the private stream: no part of the profile) */
+                else { ProfScope ps(c, CRTHIP_K_TEMPLATE); build(); }
                 memcpy(c->skel_burst, p->burst, sizeof(p->burst));
                 c->skel_yo = p->yo;
                 memcpy(c->skel_border, border_key, sizeof(border_key));
@@ -1826,12 +1757,9 @@ int crt_run_encoder_prepare(crthip_ctx *c, const crthip_params *p, bool fused)
                 signed char *dst = table_target(c, &c->d_nes_tab, &c->d_nes_tab_alt, NES_TAB_SIZE, capturing || c->nes_captured);
                 if (!dst) rc = set_err(c, CRTHIP_E_NOMEM, "hipMalloc NES sample table", hipSuccess);
                 else {
-                    if (!capturing) {
-                        ProfScope ps(c, CRTHIP_K_ACTIVE);
-                        hipLaunchKernelGGL((k_nes_table<S>), dim3((NES_TAB_SIZE + 255) / 256), dim3(256), 0, st, *p, dst);
-                    } else {
-                        hipLaunchKernelGGL((k_nes_table<S>), dim3((NES_TAB_SIZE + 255) / 256), dim3(256), 0, st, *p, dst);
-                    }
+                    const auto build = [&] { hipLaunchKernelGGL((k_nes_table<S>), dim3((NES_TAB_SIZE + 255) / 256), dim3(256), 0, st, *p, dst); };
+                    if (capturing) build();
+                    else { ProfScope ps(c, CRTHIP_K_ACTIVE); build(); }
                     c->nes_tab_black = p->black_point;
                     c->nes_tab_white = p->white_point;
                     c->nes_tab_valid = true;

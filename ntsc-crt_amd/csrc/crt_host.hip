@@ -563,12 +563,10 @@ static void launch_phosphor_rows(crthip_ctx *c, const crthip_params *p, int n, c
             const int rb = (p->outh + PHOS_ROWS - 1) / PHOS_ROWS;
             const size_t pitch = (size_t) p->outw * p->out_bpp;
             const dim3 grid((unsigned) n * (unsigned) rb);
-            if (p->blend)
-                hipLaunchKernelGGL((k_phosphor_rows<PH, true>), grid, dim3(256), 0, c->stream, n, c->sd.lines, p->outh, rb, pitch, out, ostride, ln,
+            dispatch_bools([&](auto blend) {
+                hipLaunchKernelGGL((k_phosphor_rows<PH, blend>), grid, dim3(256), 0, c->stream, n, c->sd.lines, p->outh, rb, pitch, out, ostride, ln,
                                    out_alpha_mask(p));
-            else
-                hipLaunchKernelGGL((k_phosphor_rows<PH, false>), grid, dim3(256), 0, c->stream, n, c->sd.lines, p->outh, rb, pitch, out, ostride, ln,
-                                   out_alpha_mask(p));
+            }, p->blend != 0);
         }
     });
 }

@@ -759,26 +759,19 @@ int crt_run_noise(crthip_ctx *c, const crthip_params *p, int n, const signed cha
                 const signed char *dig_blocks = c->d_vhs_dig + (size_t) c->vhs_chunks * VHS_DIG_ROW;
                 const bool mfma = c->vhs_mfma != 0;            /* the 31 x 31 jumps on the matrix cores (CRTHIP_VHS_MFMA=0: on the vector unit) */
                 const bool kn = c->call.knobs != nullptr;       /* per-field noise (crthip_fieldpass_knobs) */
-#define CRT_LAUNCH_TAIL(HOUT) do { \
-                if (kn && mfma) hipLaunchKernelGGL((k_vhs_tail<S, true, true>), dim3(n), dim3(64), 0, c->stream, *p, n, d_analog, d_inp, c->fstride, d_state, c->d_vhs_hist, HOUT, tail_row, blk_rows, dig_blocks); \
-                else if (kn) hipLaunchKernelGGL((k_vhs_tail<S, false, true>), dim3(n), dim3(64), 0, c->stream, *p, n, d_analog, d_inp, c->fstride, d_state, c->d_vhs_hist, HOUT, tail_row, blk_rows, dig_blocks); \
-                else if (mfma) hipLaunchKernelGGL((k_vhs_tail<S, true>), dim3(n), dim3(64), 0, c->stream, *p, n, d_analog, d_inp, c->fstride, d_state, c->d_vhs_hist, HOUT, tail_row, blk_rows, dig_blocks); \
-                else hipLaunchKernelGGL((k_vhs_tail<S, false>), dim3(n), dim3(64), 0, c->stream, *p, n, d_analog, d_inp, c->fstride, d_state, c->d_vhs_hist, HOUT, tail_row, blk_rows, dig_blocks); } while (0)
-                if (side) CRT_LAUNCH_TAIL(c->d_vhs_next);
-                if (kn && mfma)
-                    hipLaunchKernelGGL((k_vhs_noise<S, true, true>), dim3((n * c->vhs_chunks + 63) / 64), dim3(64), 0, ns,
+                /* k_vhs_tail<S, MFMA, KN> and k_vhs_noise<S, MFMA, KN>: every combination */
+                const auto tail = [&](unsigned *hist_out) {
+                    dispatch_bools([&](auto mfma_, auto kn_) {
+                        hipLaunchKernelGGL((k_vhs_tail<S, mfma_, kn_>), dim3(n), dim3(64), 0, c->stream, *p, n, d_analog, d_inp, c->fstride, d_state,
+                                           c->d_vhs_hist, hist_out, tail_row, blk_rows, dig_blocks);
+                    }, mfma, kn);
+                };
+                if (side) tail(c->d_vhs_next);
+                dispatch_bools([&](auto mfma_, auto kn_) {
+                    hipLaunchKernelGGL((k_vhs_noise<S, mfma_, kn_>), dim3((n * c->vhs_chunks + 63) / 64), dim3(64), 0, ns,
                                        *p, n, d_analog, d_inp, c->fstride, c->d_vhs_hist, c->d_vhs_rows, c->vhs_chunks, c->d_vhs_dig);
-                else if (kn)
-                    hipLaunchKernelGGL((k_vhs_noise<S, false, true>), dim3((n * c->vhs_chunks + 63) / 64), dim3(64), 0, ns,
-                                       *p, n, d_analog, d_inp, c->fstride, c->d_vhs_hist, c->d_vhs_rows, c->vhs_chunks, c->d_vhs_dig);
-                else if (mfma)
-                    hipLaunchKernelGGL((k_vhs_noise<S, true>), dim3((n * c->vhs_chunks + 63) / 64), dim3(64), 0, ns,
-                                       *p, n, d_analog, d_inp, c->fstride, c->d_vhs_hist, c->d_vhs_rows, c->vhs_chunks, c->d_vhs_dig);
-                else
-                    hipLaunchKernelGGL((k_vhs_noise<S, false>), dim3((n * c->vhs_chunks + 63) / 64), dim3(64), 0, ns,
-                                       *p, n, d_analog, d_inp, c->fstride, c->d_vhs_hist, c->d_vhs_rows, c->vhs_chunks, c->d_vhs_dig);
-                if (!side) CRT_LAUNCH_TAIL(c->d_vhs_hist);
-#undef CRT_LAUNCH_TAIL
+                }, mfma, kn);
+                if (!side) tail(c->d_vhs_hist);
                 if (side) {
                     if (hipEventRecord(c->ev_join, c->aux_stream) != hipSuccess ||
                         hipStreamWaitEvent(c->stream, c->ev_join, 0) != hipSuccess ||
@@ -794,12 +787,10 @@ int crt_run_noise(crthip_ctx *c, const crthip_params *p, int n, const signed cha
         constexpr int CHUNKS = (S::INPUT_SIZE + 15) / 16;
         {
             ProfScope ps(c, CRTHIP_K_NOISE);
-            if (c->call.knobs)
-                hipLaunchKernelGGL((k_noise<S, true>), dim3((n * CHUNKS + 255) / 256), dim3(256), 0, c->stream,
+            dispatch_bools([&](auto kn) {                          /* k_noise<S, KN>: per-field noise or the blob's */
+                hipLaunchKernelGGL((k_noise<S, kn>), dim3((n * CHUNKS + 255) / 256), dim3(256), 0, c->stream,
                                    *p, n, d_analog, d_inp, c->fstride, d_state, c->d_jump16);
-            else
-            hipLaunchKernelGGL((k_noise<S>), dim3((n * CHUNKS + 255) / 256), dim3(256), 0, c->stream,
-                               *p, n, d_analog, d_inp, c->fstride, d_state, c->d_jump16);
+            }, c->call.knobs != nullptr);
         }
         if (advance_rn) hipLaunchKernelGGL(k_advance_rn, dim3((n + 63) / 64), dim3(64), 0, c->stream, n, d_state, c->whole_field);
         return CRTHIP_OK;
@@ -815,12 +806,10 @@ int crt_run_vhs_chain(crthip_ctx *c, int n, crthip_state *d_state, int draw_aber
         using S = decltype(tag);
         if constexpr (S::IS_VHS) {
             const unsigned *tail_row = c->d_vhs_rows + (size_t) c->vhs_chunks * 31, *blk_rows = c->d_vhs_rows + (size_t) (c->vhs_chunks + 1) * 31;
-            if (d_set_first)
-                hipLaunchKernelGGL((k_vhs_chain<S, true>), dim3((unsigned) n_sets), dim3(64), 0, c->stream, n, d_set_first, d_state, c->d_vhs_hist,
-                                   tail_row, blk_rows, draw_aberration);
-            else
-                hipLaunchKernelGGL((k_vhs_chain<S>), dim3(1), dim3(64), 0, c->stream, n, (const int *) nullptr, d_state, c->d_vhs_hist,
-                                   tail_row, blk_rows, draw_aberration);
+            dispatch_bools([&](auto sets) {                        /* k_vhs_chain<S, SETS>: one workgroup per set, or the one stream */
+                hipLaunchKernelGGL((k_vhs_chain<S, sets>), dim3(sets ? (unsigned) n_sets : 1u), dim3(64), 0, c->stream, n, d_set_first, d_state,
+                                   c->d_vhs_hist, tail_row, blk_rows, draw_aberration);
+            }, d_set_first != nullptr);
         }
         return CRTHIP_OK;
     });

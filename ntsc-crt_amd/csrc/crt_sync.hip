@@ -698,26 +698,24 @@ int crt_run_sync(crthip_ctx *c, const crthip_params *p, int n, const signed char
         const size_t fstride = lay ? lay->fstride : c->fstride;
         const int shift = pad ? lay->shift : 0, padv = pad ? lay->padv : 0;
         const bool fpb4 = FPB4_OK && c->sync_kernel != 2 && (n >= SYNC_FPB4_MIN_FIELDS || c->sync_kernel == 3);
-#define CRTHIP_LAUNCH_SYNC(FPB, PADV) do { \
-    if (c->call.pic) \
-    hipLaunchKernelGGL((k_hsync_wave<S, FPB, PADV, 2>), dim3((n + FPB - 1) / FPB), dim3(64 * FPB), 0, c->stream, *p, n, d_inp, fstride, d_state, d_lines, \
-                       c->whole_field, advance_rn, preset_ccf, shift, padv, pad ? const_cast<signed char *>(d_inp) : nullptr); \
-    else if (c->call.knobs) \
-    hipLaunchKernelGGL((k_hsync_wave<S, FPB, PADV, 1>), dim3((n + FPB - 1) / FPB), dim3(64 * FPB), 0, c->stream, *p, n, d_inp, fstride, d_state, d_lines, \
-                       c->whole_field, advance_rn, preset_ccf, shift, padv, pad ? const_cast<signed char *>(d_inp) : nullptr); \
-    else \
-    hipLaunchKernelGGL((k_hsync_wave<S, FPB, PADV>), dim3((n + FPB - 1) / FPB), dim3(64 * FPB), 0, c->stream, *p, n, d_inp, fstride, d_state, d_lines, \
-                       c->whole_field, advance_rn, preset_ccf, shift, padv, pad ? const_cast<signed char *>(d_inp) : nullptr);   /* (padded: the library's own workspace) */ \
-    } while (0)
-        if constexpr (FPB4_OK) {
-            if (fpb4) { if (pad) CRTHIP_LAUNCH_SYNC(4, true); else CRTHIP_LAUNCH_SYNC(4, false); }
-        }
-        if (!fpb4) { if (pad) CRTHIP_LAUNCH_SYNC(1, true); else CRTHIP_LAUNCH_SYNC(1, false); }
-#undef CRTHIP_LAUNCH_SYNC
-        if (p->bloom && c->call.knobs)
-            hipLaunchKernelGGL((k_bloom<S, true>), dim3(n), dim3(256), 0, c->stream, *p, n, d_inp, fstride, d_lines);
-        else if (p->bloom)
-            hipLaunchKernelGGL((k_bloom<S>), dim3(n), dim3(256), 0, c->stream, *p, n, d_inp, fstride, d_lines);
+        /* k_hsync_wave<S, FPB, PAD, KN>: 1 field per workgroup, and 4 where their burst chains fit one wave; KN = 0 the uniform call, 1 a
+         * call with knob records, 2 one whose records carry picture knobs */
+        const int kn = c->call.pic ? 2 : c->call.knobs ? 1 : 0;
+        const int rc = dispatch_int<1, 4>(fpb4 ? 4 : 1, [&](auto fpb) { return dispatch_int<0, 1, 2>(kn, [&](auto kn_) {
+            return dispatch_bools([&](auto pad_) {
+                if constexpr (fpb == 1 || FPB4_OK) {
+                    hipLaunchKernelGGL((k_hsync_wave<S, fpb, pad_, kn_>), dim3((n + fpb - 1) / fpb), dim3(64 * fpb), 0, c->stream, *p, n, d_inp, fstride,
+                                       d_state, d_lines, c->whole_field, advance_rn, preset_ccf, shift, padv,
+                                       pad ? const_cast<signed char *>(d_inp) : nullptr);   /* (padded: the library's own workspace) */
+                    return CRTHIP_OK;
+                } else return launch_unbuilt(c, "k_hsync_wave");
+            }, pad);
+        }); });
+        if (rc) return rc;
+        if (p->bloom)
+            dispatch_bools([&](auto kn_) {                           /* k_bloom<S, KN>: max_e per field or the blob's */
+                hipLaunchKernelGGL((k_bloom<S, kn_>), dim3(n), dim3(256), 0, c->stream, *p, n, d_inp, fstride, d_lines);
+            }, c->call.knobs != nullptr);
         return CRTHIP_OK;
     });
 }
